@@ -13,7 +13,13 @@ sum 1 / 0.1 / 0.5), backward through both, Adam.  Workload = BASELINE.json confi
 per GPU, sequence length 3, SSIM + mask + auto-mask, zeros padding, 1 scale; synthetic batch resident in HBM,
 random-init nets.  N > 1: one process per GPU, DistributedDataParallel (bucketed RCCL all-reduce of 26.8 M fp32
 gradients per step), weak scaling (12 samples per GPU), no collective on the loss path.
-`value` = global_batch * K / max-over-ranks elapsed time of the K timed steps.
+`value` = global_batch * K / max-over-ranks elapsed time of the K timed steps; `ms_per_step` = that time / K.
+
+A plain run does only what `value` needs: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs DIR:
+the four losses of the last timed step and a fixed, seeded sample of both nets' parameter gradients, as DIR/<name>.npy)
+and the JSON line.  The inputs (seeded nets and batch) are identical from run to run, and every step starts from the
+seeded nets (e2e_train), so that what the steps compute is too, up to rounding.  Everything below -- the hot-path legs, kernel timings, roofline, counters, CPU baseline, other
+depth laws, input pipeline -- is measured only with --full (`python bench.py --full ...`), in the same line.
 
 The hot path alone (the part this repo implements as hand-written HIP kernels; 0.5 % of the training step) is
 measured beside it over --loss-steps steps on depth maps / poses resident in HBM: `warp_loss_ms_per_step`,
@@ -41,6 +47,7 @@ import os
 import sys
 import time
 
+T_START = time.perf_counter()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(ROOT, "sc-sfmlearner-release_amd")
 for p in (ROOT, PKG):
@@ -52,6 +59,17 @@ import torch  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6290 GB/s is the measured copy rate
 W_PHOTO, W_SMOOTH, W_GEOM = 1.0, 0.1, 0.5  # train.py:45-47 defaults used by scripts/train_resnet18_depth_256.sh
 DOMINANT_KERNEL = "pair_fwd_spec_kernel<float,true,7u,false,false>"
+
+
+# MIOpen solvers that never win on the nets' NCHW convolutions of this workload (the find picks Winograd RxS F3x2 / F2x3
+# with one group, the assembly implicit GEMMs and the 1x1 GEMMs on every one of them) but that MIOpen compiles and times
+# at the first step when no find database is there yet -- most of a cold start's minute.  (RxS F2x3 runs the same kernel
+# as its one-group form, which it ties.)  Left out of the search as defaults; the environment overrides.  The GEMM family
+# is kept: its 1x1 solvers win on 7 of the problems, and without them a step is 0.75 % slower.
+MIOPEN_SOLVERS_NEVER_CHOSEN = ("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD", "MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_BWD",
+                               "MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_WRW", "MIOPEN_DEBUG_GROUP_CONV_IMPLICIT_GEMM_HIP_FWD_XDLOPS",
+                               "MIOPEN_DEBUG_CONV_IMPLICIT_GEMM_HIP_GROUP_BWD_XDLOPS",
+                               "MIOPEN_DEBUG_GROUP_CONV_IMPLICIT_GEMM_HIP_WRW_XDLOPS", "MIOPEN_DEBUG_AMD_WINOGRAD_RXS_F2X3")
 
 
 def log(*a):
@@ -154,7 +172,7 @@ def _calibrated(out):
     return out
 
 
-PMC_LIVE_CHILD_ARGS = ["--loss-steps", "3", "--loss-warmup", "1", "--cpu-seconds", "0", "--e2e", "0", "--graph", "0",
+PMC_LIVE_CHILD_ARGS = ["--full", "--loss-steps", "3", "--loss-warmup", "1", "--cpu-seconds", "0", "--e2e", "0", "--graph", "0",
                        "--kernel-iters", "2", "--other-laws", "0", "--pmc-live", "0"]
 
 
@@ -292,11 +310,56 @@ def time_kernels(x, flags, iters, n_ref):
     return {k: _event_time(fn, iters) for k, fn in calls.items()}
 
 
-def e2e_train(args, device, world, dev_index, barrier, dist_on=False):
+def flat_sample(tensors, k=1 << 22, seed=0):
+    """A fixed, seeded sample of k entries of `tensors` flattened one after the other, fp32 (all of them when fewer)."""
+    flat = torch.cat([t.detach().reshape(-1) for t in tensors])
+    if flat.numel() <= k:
+        return flat.float().cpu()
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(seed))[:k].sort().values
+    return flat[idx.to(flat.device)].float().cpu()
+
+
+def write_outputs(dirname, arrays, limit_bytes=64 << 20):
+    """arrays {name: tensor | number} -> dirname/<name>.npy, float64 where the value is float64, else float32.
+    Refuses (before writing anything) a set larger than limit_bytes.  -> bytes written."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > limit_bytes:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {limit_bytes}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return total
+
+
+def hot_path_outputs(x, out):
+    """What a caller of one hot-path step receives: the four losses and the gradients it left on its leaves."""
+    res = {n: torch.tensor(float(v), dtype=torch.float64) for n, v in zip(("loss", "photo_loss", "smooth_loss", "geometry_loss"), out)}
+    for s, t in enumerate(x["tgt_depth"]):
+        res[f"grad_tgt_depth_s{s}"] = t.grad.detach().cpu()
+    for i, r in enumerate(x["ref_depths"]):
+        for s, t in enumerate(r):
+            res[f"grad_ref{i}_depth_s{s}"] = t.grad.detach().cpu()
+    res["grad_poses"] = torch.stack([p.grad.detach() for p in x["poses"]]).cpu()
+    res["grad_poses_inv"] = torch.stack([p.grad.detach() for p in x["poses_inv"]]).cpu()
+    return res
+
+
+def e2e_train(args, device, world, dev_index, barrier, dist_on=False, keep_outputs=False):
     """K timed whole training steps of BASELINE.json's metric (train.py:249-286): 3 DispResNet + 4 PoseResNet18
     forwards (PyTorch-ROCm / MIOpen), the HIP loss path, backward, Adam; data parallel with
     DistributedDataParallel (train.wrap_ddp) when world > 1.  Synthetic batch resident in HBM, random-init nets.
-    W untimed warm-up steps, then exactly K steps between barrier + synchronize, max over ranks."""
+    W untimed warm-up steps, then exactly K steps between barrier + synchronize, max over ranks.
+    Every step starts from the same parameters, the seeded initial nets' (one on-device copy of the 4-byte trainable
+    parameters in front of it, 107 MB at configs[1], ~0.04 % of the step): each step does all of the work of a training step --
+    forward, loss, backward, Adam update -- on the same inputs and computes the same losses and gradients up to
+    rounding, run after run.  (A K-step trajectory does not: the reductions of the nets' backward and of the loss path
+    are not ordered, and Adam's sign-normalised first steps carry that rounding into the parameters, which then part.)
+    keep_outputs: also return (`outputs`) the last step's four losses and a sample of both nets' parameter gradients."""
     import argparse as _ap
 
     import models
@@ -321,20 +384,42 @@ def e2e_train(args, device, world, dev_index, barrier, dist_on=False):
               {"params": [p for p in pose_net.parameters() if p.requires_grad]}]
     n_grad = sum(p.numel() for g in params for p in g["params"])
     opt = torch.optim.Adam(params, lr=1e-4, betas=(0.9, 0.999))
+    trainable = [p for g in params for p in g["params"]]
+    start = [p.detach().clone() for p in trainable]
+
+    def step():
+        with torch.no_grad():
+            torch._foreach_copy_(trainable, start)
+        return T.train_step(targs, disp_net, pose_net, opt, tgt, refs, K)
+
     g = torch.Generator().manual_seed(1234 + int(os.environ.get("RANK", 0)))
     mk = lambda: ((torch.rand(args.batch, 3, args.height, args.width, generator=g) - 0.45) / 0.225).to(device)
     tgt, refs = mk(), [mk() for _ in range(args.n_ref)]
     from scsfm_hip import synth
     K = synth.intrinsics(__import__("numpy").random.default_rng(int(os.environ.get("RANK", 0))), args.batch, args.height,
                          args.width, args.dataset).to(device)
-    for _ in range(args.warmup):
-        T.train_step(targs, disp_net, pose_net, opt, tgt, refs, K)
+    tw = time.perf_counter()
+    for i in range(args.warmup):
+        step()
+        if i == 0:
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            log(f"[bench] first warm-up step {t1 - tw:.2f} s (kernel compilation / algorithm search of the nets included)")
     barrier()
     t0 = time.perf_counter()
+    log(f"[bench] {args.warmup} warm-up steps {t0 - tw:.2f} s")
     for _ in range(args.steps):
-        loss = T.train_step(targs, disp_net, pose_net, opt, tgt, refs, K)[0]
+        losses = step()
     barrier()
     dt = time.perf_counter() - t0
+    loss = losses[0]
+    outputs = None
+    if keep_outputs:
+        outputs = {n: torch.tensor(float(v), dtype=torch.float64)
+                   for n, v in zip(("loss", "photo_loss", "smooth_loss", "geometry_loss"), losses)}
+        for name, net in (("disp_net", disp_net), ("pose_net", pose_net)):
+            grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in net.parameters()]
+            outputs[f"{name}_gradients_sample"] = flat_sample(grads)
     ranks = 1
     if dist_on:
         import torch.distributed as dist
@@ -351,7 +436,8 @@ def e2e_train(args, device, world, dev_index, barrier, dist_on=False):
     if targs.exact_mask_normalisation and dist_on:
         hip_dist.disable_exact_normalisation()  # (the hot-path legs below time the default mode)
     return {"elapsed_s": dt, "ranks": ranks, "final_loss": final, "trainable_parameters": n_grad,
-            "model": f"DispResNet{args.resnet_layers} + PoseResNet18, random init, fp32 (MIOpen convolutions)"}
+            "model": f"DispResNet{args.resnet_layers} + PoseResNet18, random init, fp32 (MIOpen convolutions)",
+            "outputs": outputs}
 
 
 def cpu_baseline(args, budget_s):
@@ -445,6 +531,46 @@ def self_launch(n_gpus, argv):
     return subprocess.call(cmd, env=env)
 
 
+def headline(args, world, backend, dist_on, e2e, hot_rate=None, loss_ms=None):
+    """The fields of every result line: the headline figure (the training rate; with --e2e 0 the hot-path rate, and the
+    line says so), its unit and time per step, the workload and how it was spread over the ranks."""
+    shape = (args.dataset, args.height, args.width, args.batch, args.n_ref, args.resnet_layers)
+    # which BASELINE.json config this run is the per-GPU workload of ([1] and [2] share theirs)
+    named = {("kitti", 256, 832, 12, 2, 18): "configs[1]", ("kitti", 256, 832, 8, 2, 50): "configs[3]",
+             ("nyu", 256, 320, 16, 4, 18): "configs[4] (batch 16/GPU)", ("kitti", 256, 832, 4, 2, 18): "configs[0] shape"}
+    workload = (f"{named.get(shape, 'custom')}: {args.dataset} {args.height}x{args.width}, batch {args.batch}/GPU, {args.n_ref} refs "
+                f"(seq {args.n_ref + 1}), ResNet{args.resnet_layers} DispNet + ResNet18 PoseNet, ssim+mask+auto-mask, "
+                f"zeros padding, 1 scale")
+    if e2e is not None:
+        value = world * args.batch * args.steps / e2e["elapsed_s"]
+        ms_per_step = e2e["elapsed_s"] / args.steps * 1e3
+        metric = "train images/sec (+ warp-loss ms/step) KITTI 256x832 RN18" if shape[:3] == ("kitti", 256, 832) and \
+            args.resnet_layers == 18 else f"train images/sec (+ warp-loss ms/step) {args.dataset} {args.height}x{args.width} RN{args.resnet_layers}"
+        parallelism = (f"ddp{world}: one process per GPU, DistributedDataParallel, bucketed {backend} all-reduce of "
+                       f"{e2e['trainable_parameters'] * 4 / 1e6:.1f} MB of fp32 gradients per step; loss path sharded "
+                       f"by batch, " + ("one all-reduce of the pairs' raw sums per step (exact mask normalisation)"
+                                       if args.exact else "no loss-path collective")) if dist_on else "1 GPU"
+    else:  # --e2e 0 (profiling): say plainly that this is NOT the training rate
+        value, ms_per_step = hot_rate, loss_ms
+        metric = "images/sec through the warp+loss hot path ONLY (--e2e 0: nets and optimizer not run)"
+        parallelism = f"dp{world} (batch shards, no loss-path collective)"
+    return {
+        "metric": metric,
+        "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": workload, "global_batch": world * args.batch, "parallelism": parallelism,
+                   "memory_format": "channels_last (nets only; --channels-last 1, not the default)" if args.channels_last else "contiguous (NCHW)"},
+        # ranks an all-reduce on the process group actually spanned: `rccl_ranks` only when that group is nccl (= RCCL)
+        ("rccl_ranks" if backend in (None, "nccl") else "collective_ranks"): e2e["ranks"] if e2e is not None else world,
+        "collective_backend": backend,
+        "exact_mask_normalisation": bool(args.exact),
+        "train": None if e2e is None else {"train_images_per_sec": round(value, 2), "ms_per_step": round(ms_per_step, 3),
+                                           "final_loss": e2e["final_loss"], "model": e2e["model"],
+                                           "trainable_parameters": e2e["trainable_parameters"]},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -490,7 +616,20 @@ def main():
     ap.add_argument("--pmc-live-timeout", type=float, default=120.0, help="seconds allowed per counter pass")
     ap.add_argument("--exact", type=int, default=0, help="1: exact mask normalisation (scsfm_hip.dist: one all-reduce of "
                                                          "the pairs' raw sums per step) in the distributed legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the hot-path legs (eager, one autograd node, "
+                         "graph replay), kernel timings, roofline and counters, other depth laws, CPU baseline, input "
+                         "pipeline.  Without it a run sets up, warms up, times --steps steps and prints the line; the "
+                         "options of those legs (--loss-steps, --kernel-iters, --cpu-seconds, --pmc-live, --other-laws, "
+                         "--data loader, ...) then have no effect, except that --e2e 0 still times its hot-path leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, <= 64 MB): the four losses and a seeded 4 M-entry sample of each net's "
+                         "parameter gradients; with --e2e 0 the losses and the gradients of the depth maps and poses")
     args = ap.parse_args()
+    if not args.channels_last:  # (set before the first convolution: MIOpen reads them then)
+        for k in MIOPEN_SOLVERS_NEVER_CHOSEN:
+            os.environ.setdefault(k, "0")
 
     rank = int(os.environ.get("RANK", 0))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
@@ -543,13 +682,21 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    def finish():
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    dump = args.dump_outputs if rank == 0 else None
+
     # ---------------------------------------------------------------------------------------------------
     # 1. BASELINE.json's metric: whole training steps (nets + HIP loss path + backward + Adam), W warm-up + K timed
     # ---------------------------------------------------------------------------------------------------
     e2e = None
     if args.e2e:
+        log(f"[bench] set-up {time.perf_counter() - T_START:.2f} s")
         try:
-            e2e = e2e_train(args, device, world, dev_index, barrier, dist_on)
+            e2e = e2e_train(args, device, world, dev_index, barrier, dist_on, keep_outputs=dump is not None)
         except Exception as exc:
             import traceback
             traceback.print_exc()
@@ -561,6 +708,13 @@ def main():
                     pass
             sys.exit(3)  # a broken training step is a broken bench: no JSON line, non-zero status
         torch.cuda.empty_cache()
+        if dump:
+            write_outputs(dump, e2e.pop("outputs"))
+        if not args.full:  # a plain run: the training rate is all it measures
+            if rank == 0:
+                print(json.dumps({**headline(args, world, backend, dist_on, e2e), "library": ident}), flush=True)
+            finish()
+            return
 
     # ---------------------------------------------------------------------------------------------------
     # 2. the hot path alone (loss forward + backward on resident depth maps / poses)
@@ -594,6 +748,7 @@ def main():
     lib.call("scsfm_profile_end", ctypes.addressof(prof_mean), ctypes.addressof(prof_min), ctypes.addressof(prof_n))
     in_step_us = (prof_mean.value, prof_min.value, prof_n.value)
     eager_vals = [float(v.detach()) for v in out]
+    hot_dump = hot_path_outputs(x, out) if dump and e2e is None else None
     del out  # nothing may keep the eager step's autograd graph (and its stream-bound AccumulateGrad nodes) alive
     import gc
     gc.collect()
@@ -602,15 +757,16 @@ def main():
     # Measured before any graph is captured: a live capture keeps stream-bound autograd nodes alive and slows later
     # eager steps down.
     single = None
-    try:
-        se, so = timed(lambda: hot_path_step_single_node(LF, x, flags))
-        svals = [float(v.detach()) for v in so]
-        del so
-        gc.collect()
-        single = {"eager_ms_per_step": round(se / args.loss_steps * 1e3, 4),
-                  "losses_match": all(abs(a - b) <= 1e-6 * max(1.0, abs(b)) for a, b in zip(svals, eager_vals))}
-    except Exception as exc:
-        single = {"error": f"{type(exc).__name__}: {exc}"}
+    if args.full:
+        try:
+            se, so = timed(lambda: hot_path_step_single_node(LF, x, flags))
+            svals = [float(v.detach()) for v in so]
+            del so
+            gc.collect()
+            single = {"eager_ms_per_step": round(se / args.loss_steps * 1e3, 4),
+                      "losses_match": all(abs(a - b) <= 1e-6 * max(1.0, abs(b)) for a, b in zip(svals, eager_vals))}
+        except Exception as exc:
+            single = {"error": f"{type(exc).__name__}: {exc}"}
     graph_err = None
     if args.graph and ((world == 1 and not dist_on) or args.graph > 1):
         # the same step captured once into a HIP graph and replayed: identical kernels and results, one launch
@@ -623,12 +779,17 @@ def main():
             launch = "HIP graph replay of the captured step (torch.cuda.CUDAGraph)"
             gvals = [float(v.detach()) for v in out]
             assert all(abs(a - b) <= 1e-6 * max(1.0, abs(b)) for a, b in zip(gvals, eager_vals)), (gvals, eager_vals)
+            if hot_dump is not None:  # the replayed step is the timed path: its outputs replace the eager leg's
+                hot_dump = hot_path_outputs(x, out)
         except Exception as exc:  # keep the eager measurement, say why the graph leg is missing
             graph_err = f"{type(exc).__name__}: {exc}"
             loss_elapsed, gvals = eager_elapsed, eager_vals
     else:
         gvals = eager_vals
     loss, photo, smooth, geom = gvals
+    if hot_dump is not None:
+        write_outputs(dump, hot_dump)
+        hot_dump = None
 
     # extension leg as a graph replay
     if single is not None and "error" not in single and args.graph and ((world == 1 and not dist_on) or args.graph > 1):
@@ -645,6 +806,12 @@ def main():
     n_px = args.batch * args.height * args.width
     loss_ms = loss_elapsed / args.loss_steps * 1e3
     hot_rate = world * args.batch * args.loss_steps / loss_elapsed
+    if not args.full:  # --e2e 0 without --full: the hot-path rate is the headline, nothing else is measured
+        if rank == 0:
+            print(json.dumps({**headline(args, world, backend, dist_on, e2e, hot_rate, loss_ms),
+                              "warp_loss_ms_per_step": round(loss_ms, 4), "library": ident}), flush=True)
+        finish()
+        return
 
     kt = time_kernels(x, flags, args.kernel_iters, args.n_ref)
     n_pairs = 2 * args.n_ref
@@ -749,44 +916,12 @@ def main():
                   kt["pairs_fwd_spec"] + kt["smooth_fwd"]) + kt["pairs_bwd_after_spec"] + kt["smooth_bwd"]
 
     if rank == 0:
-        shape = (args.dataset, args.height, args.width, args.batch, args.n_ref, args.resnet_layers)
-        # which BASELINE.json config this run is the per-GPU workload of ([1] and [2] share theirs)
-        named = {("kitti", 256, 832, 12, 2, 18): "configs[1]", ("kitti", 256, 832, 8, 2, 50): "configs[3]",
-                 ("nyu", 256, 320, 16, 4, 18): "configs[4] (batch 16/GPU)", ("kitti", 256, 832, 4, 2, 18): "configs[0] shape"}
-        workload = (f"{named.get(shape, 'custom')}: {args.dataset} {args.height}x{args.width}, batch {args.batch}/GPU, {args.n_ref} refs "
-                    f"(seq {args.n_ref + 1}), ResNet{args.resnet_layers} DispNet + ResNet18 PoseNet, ssim+mask+auto-mask, "
-                    f"zeros padding, 1 scale")
-        if e2e is not None:
-            value = world * args.batch * args.steps / e2e["elapsed_s"]
-            ms_per_step = e2e["elapsed_s"] / args.steps * 1e3
-            metric = "train images/sec (+ warp-loss ms/step) KITTI 256x832 RN18" if shape[:3] == ("kitti", 256, 832) and \
-                args.resnet_layers == 18 else f"train images/sec (+ warp-loss ms/step) {args.dataset} {args.height}x{args.width} RN{args.resnet_layers}"
-            parallelism = (f"ddp{world}: one process per GPU, DistributedDataParallel, bucketed {backend} all-reduce of "
-                           f"{e2e['trainable_parameters'] * 4 / 1e6:.1f} MB of fp32 gradients per step; loss path sharded "
-                           f"by batch, " + ("one all-reduce of the pairs' raw sums per step (exact mask normalisation)"
-                                           if args.exact else "no loss-path collective")) if dist_on else "1 GPU"
-        else:  # --e2e 0 (profiling): say plainly that this is NOT the training rate
-            value, ms_per_step = hot_rate, loss_ms
-            metric = "images/sec through the warp+loss hot path ONLY (--e2e 0: nets and optimizer not run)"
-            parallelism = f"dp{world} (batch shards, no loss-path collective)"
-        res = {
-            "metric": metric,
-            "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": workload, "global_batch": world * args.batch, "parallelism": parallelism,
-                       "memory_format": "channels_last (nets only; --channels-last 1, not the default)" if args.channels_last else "contiguous (NCHW)"},
-            # ranks an all-reduce on the process group actually spanned: `rccl_ranks` only when that group is nccl (= RCCL)
-            ("rccl_ranks" if backend in (None, "nccl") else "collective_ranks"): e2e["ranks"] if e2e is not None else world,
-            "collective_backend": backend,
-            "exact_mask_normalisation": bool(args.exact),
-            "train": None if e2e is None else {"train_images_per_sec": round(value, 2), "ms_per_step": round(ms_per_step, 3),
-                                               "final_loss": e2e["final_loss"], "model": e2e["model"],
-                                               "trainable_parameters": e2e["trainable_parameters"]},
+        res = headline(args, world, backend, dist_on, e2e, hot_rate, loss_ms)
+        res.update({
             # ---- the hot path alone ----
             "warp_loss_ms_per_step": round(loss_ms, 4),
             "hot_path_images_per_sec": round(hot_rate, 2),
-            "warp_loss_share_of_train_step": None if e2e is None else round(loss_ms / ms_per_step, 5),
+            "warp_loss_share_of_train_step": None if e2e is None else round(loss_ms / (e2e["elapsed_s"] / args.steps * 1e3), 5),
             "warp_loss": {"launch": launch, "steps": args.loss_steps, "warmup": args.loss_warmup,
                           "depth_law": args.depth, "eager_ms_per_step": round(eager_elapsed / args.loss_steps * 1e3, 4),
                           "graph_error": graph_err, "single_autograd_node": single,
@@ -800,7 +935,7 @@ def main():
             # the dominant kernel on the other two depth laws (same bytes, same peak; --other-laws 0 skips the leg)
             "roofline_other_depth_laws": other_laws or None,
             "library": ident,
-        }
+        })
         if world == 1 and args.cpu_seconds > 0:
             res["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         if world == 1 and args.data == "loader":
@@ -808,9 +943,7 @@ def main():
             import loader_bench
             res["input_pipeline"] = loader_bench.run(args.batch, args.height, args.width, args.n_ref + 1)
         print(json.dumps(res), flush=True)
-    if dist_on:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

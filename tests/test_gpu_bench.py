@@ -1,5 +1,6 @@
 """bench.py's contract on hardware, at a reduced size: one JSON line whose `value` is the training rate
-(BASELINE.json's metric) with the hot-path figures, roofline and CPU baseline beside it; and the two-rank control
+(BASELINE.json's metric), with the hot-path figures, roofline and CPU baseline beside it under --full and without
+them in a plain run, which can also write its outputs (--dump-outputs); and the two-rank control
 flow (both ranks on the one GPU, gloo) with DistributedDataParallel around the nets -- the path that died in
 round 1 -- reporting the number of ranks its collective spanned."""
 import json
@@ -52,7 +53,7 @@ def _last_json(out):
 
 def test_single_gpu_line_has_the_contract_fields():
     env = dict(os.environ, SCSFM_CUDNN_BENCHMARK="0", MIOPEN_FIND_MODE="FAST")
-    out = _run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--cpu-seconds", "4"], env)
+    out = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *SMALL, "--cpu-seconds", "4"], env)
     r = _last_json(out)
     assert r["metric"].startswith("train images/sec") and r["unit"] == "images/s" and r["n_gpus"] == 1
     assert r["steps"] == 2 and r["warmup"] == 1 and r["higher_is_better"] is True and r["vs_baseline"] is None
@@ -84,6 +85,39 @@ def test_single_gpu_line_has_the_contract_fields():
     assert r["collective_backend"] is None and r["rccl_ranks"] == 1
 
 
+def test_plain_run_times_the_training_steps_only_and_dumps_their_outputs(tmp_path):
+    """Without --full the line carries the headline fields and nothing of the other legs; --dump-outputs writes the last
+    timed step's losses and gradient samples of both nets, float32 / float64, within 64 MB; and a second run with the same
+    arguments computes the same outputs up to rounding (every step starts from the seeded nets)."""
+    import numpy as np
+    env = dict(os.environ, SCSFM_CUDNN_BENCHMARK="0", MIOPEN_FIND_MODE="FAST")
+    runs = []
+    for n in range(2):
+        out = _run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--steps", "3", "--dump-outputs", str(tmp_path / str(n))], env)
+        runs.append((_last_json(out), {p.name: np.load(p) for p in (tmp_path / str(n)).iterdir()}))
+    r, files = runs[0]
+    assert r["metric"].startswith("train images/sec") and r["unit"] == "images/s" and r["dtype"] == "f32"
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["higher_is_better"] is True
+    assert r["value"] > 0 and abs(r["value"] - 2 * 3 / (r["ms_per_step"] * 3e-3)) < 1e-2 * r["value"]
+    for moved in ("warp_loss", "warp_loss_ms_per_step", "roofline", "roofline_other_depth_laws", "cpu_baseline", "input_pipeline"):
+        assert moved not in r, moved
+    assert set(files) == {"loss.npy", "photo_loss.npy", "smooth_loss.npy", "geometry_loss.npy",
+                          "disp_net_gradients_sample.npy", "pose_net_gradients_sample.npy"}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert float(files["loss.npy"]) == r["train"]["final_loss"]
+    assert files["disp_net_gradients_sample.npy"].size == 1 << 22
+    # the same outputs, run after run, up to the rounding of unordered fp32 reductions: losses to 1e-5 relative, gradient
+    # samples to 1e-2 of their largest entry (the pose gradients' own fp32 noise is 0.15-1.5 % of scale, tests/test_gpu_parity.py;
+    # measured at configs[1] between two runs: 1.3e-4 / 9.4e-4 of scale for the two nets, losses bit-identical)
+    other = runs[1][1]
+    for name, a in files.items():
+        b = other[name].astype(np.float64)
+        scale = max(float(np.abs(a).max()), 1e-30)
+        tol = 1e-5 if a.ndim == 0 else 1e-2
+        assert float(np.abs(a.astype(np.float64) - b).max()) <= tol * scale, (name, float(np.abs(a - b).max()), scale)
+
+
 def test_hbm_counters_are_measured_in_the_run():
     """`roofline.traffic` MEASURED by the run itself (round 6, --pmc-live): two child runs of the loss-path leg under
     `rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE`, on this box and the loaded library; here at a reduced shape (--pmc-live 2: the
@@ -94,7 +128,7 @@ def test_hbm_counters_are_measured_in_the_run():
     if shutil.which("rocprofv3") is None:
         pytest.skip("no rocprofv3 on this box")
     env = dict(os.environ, SCSFM_CUDNN_BENCHMARK="0", MIOPEN_FIND_MODE="FAST")
-    out = _run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--cpu-seconds", "0", "--e2e", "0", "--other-laws", "0",
+    out = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *SMALL, "--cpu-seconds", "0", "--e2e", "0", "--other-laws", "0",
                 "--pmc-live", "2"], env)
     r = _last_json(out)
     rf = r["roofline"]
@@ -132,7 +166,7 @@ def test_one_rank_over_rccl(exact):
     gradient_as_bucket_view), training steps in the default and in the exact mask-normalisation mode (all-reduce of the
     pairs' raw sums on a HIP tensor + re-finalisation), the hot path eager and as a HIP-graph replay (--graph 2)."""
     env = dict(os.environ, SCSFM_CUDNN_BENCHMARK="0", MIOPEN_FIND_MODE="FAST", MASTER_PORT=str(_free_port()))
-    out = _run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--cpu-seconds", "0", "--force-dist", "nccl",
+    out = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *SMALL, "--cpu-seconds", "0", "--force-dist", "nccl",
                 "--exact", str(exact), "--graph", "2"], env)
     r = _last_json(out)
     assert r["collective_backend"] == "nccl" and r["rccl_ranks"] == 1 and r["n_gpus"] == 1
