@@ -55,6 +55,23 @@ class DepthDecoder(nn.Module):
         self.sigmoid = nn.Sigmoid()
 
     def forward(self, feats):
+        if self.fused_path_applies(feats):
+            return self.forward_fused(feats)
+        return self.forward_reference(feats)
+
+    def fused_path_applies(self, feats):
+        """CUDA fp32 contiguous NCHW features and weights take the fused HIP glue (forward_fused); CPU, fp64 and
+        channels_last run the reference chain (forward_reference) unchanged."""
+        return all(f.is_cuda and f.dtype == torch.float32 and f.dim() == 4 and f.is_contiguous() for f in feats) and \
+            all(self._conv(k).weight.dtype == torch.float32 and self._conv(k).weight.is_contiguous()
+                for k in range(len(self.decoder)))
+
+    def _conv(self, k):
+        """the nn.Conv2d of block k (a ConvBlock's or a head's Conv3x3), called without its pad"""
+        m = self.decoder[k]
+        return m.conv.conv if isinstance(m, ConvBlock) else m.conv
+
+    def forward_reference(self, feats):
         outputs = []
         x = feats[-1]
         for i in range(4, -1, -1):
@@ -65,6 +82,26 @@ class DepthDecoder(nn.Module):
             x = self.decoder[self._up[(i, 1)]](x)
             if i in self._head:
                 outputs.append(self.alpha * self.sigmoid(self.decoder[self._head[i]](x)) + self.beta)
+        return outputs[::-1]
+
+    def forward_fused(self, feats):
+        """forward_reference with every reflection pad, ELU, upsampling and concatenation done by the HIP kernels of
+        scsfm_hip.decoder: the same modules' convolutions (``Conv3x3.conv``, ``_conv``) receive the same padded tensors, bit for
+        bit.  Per level i: a = conv (i,0)(P), P = R(cat[U(E(a)), f_{i-1}]), b = conv (i,1)(P), Q = R(E(b)); Q is
+        the input of both conv (i-1,0) and head i (the reference pads E(b) once for each)."""
+        from scsfm_hip import decoder as D
+        conv = lambda k, x: self._conv(k)(x)  # noqa: E731
+        outputs = []
+        x = D.pad(feats[-1])
+        for i in range(4, -1, -1):
+            a = conv(self._up[(i, 0)], x)
+            x = D.up_cat_pad(a, feats[i - 1] if self.use_skips and i > 0 else None)
+            b = conv(self._up[(i, 1)], x)
+            if i == 0 and i not in self._head:
+                break
+            x = D.elu_pad(b)
+            if i in self._head:
+                outputs.append(self.alpha * self.sigmoid(conv(self._head[i], x)) + self.beta)
         return outputs[::-1]
 
 

@@ -53,28 +53,30 @@ class ScsfmError(RuntimeError):
 
 
 class CLib:
-    """A loaded implementation of the C ABI.  Every declared symbol must be present."""
+    """A loaded implementation of the C ABI of ``header`` (default include/scsfm_hip.h).  Every declared symbol must be
+    present and ``<prefix>abi_version()`` must return ``abi``; the source id is read from ``<prefix>source_id``."""
 
-    def __init__(self, path):
+    def __init__(self, path, header=HEADER, abi=ABI_VERSION, prefix="scsfm_"):
         self.path = path
         self._dll = ctypes.CDLL(path)
-        self.decls = parse_header()
+        self.decls = parse_header(header)
         self._fn = {}
+        self._prefix = prefix
         for name, (ret, argtypes) in self.decls.items():
             try:
                 fn = getattr(self._dll, name)
             except AttributeError as e:
-                raise ScsfmError(f"{path} does not export {name} (declared in {HEADER})") from e
+                raise ScsfmError(f"{path} does not export {name} (declared in {header})") from e
             fn.restype = ret
             fn.argtypes = argtypes
             self._fn[name] = fn
-        if self._dll.scsfm_abi_version() != ABI_VERSION:
+        if self._fn[prefix + "abi_version"]() != abi:
             raise ScsfmError(f"{path}: ABI version mismatch")
 
     def source_id(self):
-        """The source hash compiled into the binary (scsfm_hip/build.py: source_id)."""
+        """The source hash compiled into the binary (scsfm_hip/build.py: source_id / nets_source_id)."""
         buf = ctypes.create_string_buffer(64)
-        self._fn["scsfm_source_id"](buf, 64)
+        self._fn[self._prefix + "source_id"](buf, 64)
         return buf.value.decode()
 
     def call(self, name, *args):
@@ -118,3 +120,33 @@ def get() -> CLib:
                     raise ScsfmError(f"{LIB_PATH}: its source id {lib.source_id()} is not the tree's {_build.source_id()}")
                 _lib = lib
     return _lib
+
+
+NETS_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_nets.h")
+NETS_LIB_PATH = os.path.join(HERE, "libscsfm_nets.so")
+NETS_ABI_VERSION = 1  # include/scsfm_nets.h
+_nets = None
+
+
+def get_nets() -> CLib:
+    """The nets library, libscsfm_nets.so (singleton): the fused glue of the depth decoder (include/scsfm_nets.h).
+    Built in-tree with hipcc when it is missing or stale, under the same file-lock scheme as ``get()``; raises when that
+    is impossible."""
+    global _nets
+    if _nets is None:
+        with _lock:
+            if _nets is None:
+                from . import build as _build
+                if _build.nets_is_stale():
+                    have = _build.binary_source_id(NETS_LIB_PATH)
+                    try:
+                        _build.build_nets()
+                    except Exception as e:
+                        raise ScsfmError(f"{NETS_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(NETS_LIB_PATH, NETS_HEADER, NETS_ABI_VERSION, "scsfm_nets_")
+                if lib.source_id() != _build.nets_source_id():
+                    raise ScsfmError(f"{NETS_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.nets_source_id()}")
+                _nets = lib
+    return _nets

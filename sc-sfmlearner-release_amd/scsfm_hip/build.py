@@ -1,9 +1,11 @@
-"""Build libscsfm_hip.so (gfx950) in-tree with hipcc.
+"""Build libscsfm_hip.so and libscsfm_nets.so (gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
-The shared object is plain HIP + a C ABI (include/scsfm_hip.h); it does not link against torch.
-It is written next to this file so that it travels with the source tree to the GPU box.
+Each shared object is plain HIP + a C ABI (include/scsfm_hip.h: the loss path from csrc/*.hip; include/scsfm_nets.h:
+the depth decoder's fused glue from csrc_nets/*.hip); neither links against torch.  They are written next to this file
+so that they travel with the source tree to the GPU box.  The two are separate targets with separate source ids, so
+that an edit of the nets' kernels leaves the loss library's id (to which recorded PMC counters are tied) unchanged.
 
 Safe for N processes at once (torchrun: every rank calls ``_lib.get()`` lazily, and ``*.so`` is git-ignored, so a fresh
 clone on an 8-GPU node has no library): the build runs under an exclusive ``flock`` on ``libscsfm_hip.so.lock``, the
@@ -27,6 +29,9 @@ CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 LIB = os.path.join(HERE, "libscsfm_hip.so")
 LOCK = LIB + ".lock"
 LOG = LIB + ".buildlog"
+INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
+NETS_CSRC = os.path.join(os.path.dirname(HERE), "csrc_nets")
+NETS_LIB = os.path.join(HERE, "libscsfm_nets.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -43,7 +48,26 @@ def sources():
 
 def deps():
     return sources() + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + \
-        [os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_hip.h")]
+        [os.path.join(INCLUDE, "scsfm_hip.h")]
+
+
+def nets_sources():
+    return sorted(glob.glob(os.path.join(NETS_CSRC, "*.hip")))
+
+
+def nets_deps():
+    return nets_sources() + sorted(glob.glob(os.path.join(NETS_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_nets.h")]
+
+
+def _hash(files, extra=()):
+    h = hashlib.sha256()
+    for path in files:
+        h.update(os.path.basename(path).encode())
+        h.update(open(path, "rb").read())
+    h.update(" ".join(FLAGS).encode())
+    if extra:
+        h.update(b"\0extra:" + " ".join(extra).encode())
+    return h.hexdigest()[:16]
 
 
 def source_id(extra=()):
@@ -52,20 +76,18 @@ def source_id(extra=()):
     of a non-default build, so that a tuning variant can never carry the default library's id (bench.py ties PMC
     counters to a library by this id).  It is compiled into the binary (scsfm_source_id) so that a loaded .so can be
     tied to the sources next to it."""
-    h = hashlib.sha256()
     files = deps()
     if any("SCSFM_WITH_MARCH" in e or "variants" in e for e in extra):
         # tuning builds compile the experimental kernels of variants/src/ in: an edit there must change the id too (round-5
         # advisor finding: PMC counters could be attributed to a stale variant binary)
         vsrc = os.path.join(os.path.dirname(os.path.dirname(HERE)), "variants", "src")
         files = files + sorted(p for p in glob.glob(os.path.join(vsrc, "*")) if os.path.isfile(p))
-    for path in files:
-        h.update(os.path.basename(path).encode())
-        h.update(open(path, "rb").read())
-    h.update(" ".join(FLAGS).encode())
-    if extra:
-        h.update(b"\0extra:" + " ".join(extra).encode())
-    return h.hexdigest()[:16]
+    return _hash(files, extra)
+
+
+def nets_source_id():
+    """source_id() of libscsfm_nets.so: its own sources (csrc_nets/, include/scsfm_nets.h) and the compiler flags."""
+    return _hash(nets_deps())
 
 
 def binary_source_id(path=LIB):
@@ -87,9 +109,13 @@ def is_stale():
     return binary_source_id(LIB) != source_id()
 
 
+def nets_is_stale():
+    return binary_source_id(NETS_LIB) != nets_source_id()
+
+
 @contextlib.contextmanager
-def _build_lock():
-    fd = os.open(LOCK, os.O_CREAT | os.O_RDWR, 0o644)
+def _build_lock(lock=None):
+    fd = os.open(lock or LOCK, os.O_CREAT | os.O_RDWR, 0o644)
     try:
         fcntl.flock(fd, fcntl.LOCK_EX)
         yield
@@ -107,33 +133,44 @@ def build(force=False, verbose=True, extra=()):
     further compiler flags (tuning knobs); the binary then carries source_id(extra), which differs from the tree's
     default id, so the loader treats it as stale for the default configuration and rebuilds on the next plain get()."""
     extra = tuple(extra)
-    want = source_id(extra)
-    if not force and binary_source_id(LIB) == want:
-        return LIB
-    with _build_lock():
+    return _build(LIB, source_id(extra), sources(), extra, force, verbose)
+
+
+def build_nets(force=False, verbose=True):
+    """build() for libscsfm_nets.so: every .hip file under csrc_nets/, against include/scsfm_nets.h."""
+    return _build(NETS_LIB, nets_source_id(), nets_sources(), ("-I", INCLUDE), force, verbose)
+
+
+def _build(lib, want, srcs, extra, force, verbose):
+    if not force and binary_source_id(lib) == want:
+        return lib
+    with _build_lock(lib + ".lock"):
         # (another process may have built while this one waited for the lock)
-        if not force and binary_source_id(LIB) == want:
-            return LIB
+        if not force and binary_source_id(lib) == want:
+            return lib
         hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+        name = os.path.basename(lib)
         if not os.path.exists(hipcc):
-            raise RuntimeError("hipcc not found: libscsfm_hip.so cannot be built on this machine")
-        fd, tmp = tempfile.mkstemp(prefix="libscsfm_hip.", suffix=f".{os.getpid()}.tmp", dir=HERE)
+            raise RuntimeError(f"hipcc not found: {name} cannot be built on this machine")
+        fd, tmp = tempfile.mkstemp(prefix=name[:-len(".so")] + ".", suffix=f".{os.getpid()}.tmp", dir=HERE)
         os.close(fd)
         try:
-            cmd = [hipcc, *FLAGS, f'-DSCSFM_SOURCE_ID="{want}"', *extra, "-o", tmp, *sources()]
+            cmd = [hipcc, *FLAGS, f'-DSCSFM_SOURCE_ID="{want}"', *extra, "-o", tmp, *srcs]
             if verbose:
                 print("[scsfm_hip.build]", " ".join(cmd), flush=True)
             subprocess.run(cmd, check=True)
             os.chmod(tmp, 0o755)
-            os.replace(tmp, LIB)
-            with open(LOG, "a") as f:  # who built what (tests/test_build_race.py counts the lines)
+            os.replace(tmp, lib)
+            with open(lib + ".buildlog", "a") as f:  # who built what (tests/test_build_race.py counts the lines)
                 f.write(f"{want} {os.getpid()}\n")
         finally:
             if os.path.exists(tmp):
                 os.unlink(tmp)
-    return LIB
+    return lib
 
 
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
+    build_nets(force="--force" in sys.argv)
     print(LIB)
+    print(NETS_LIB)
