@@ -150,3 +150,33 @@ def get_nets() -> CLib:
                                      f"{_build.nets_source_id()}")
                 _nets = lib
     return _nets
+
+
+EVAL_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_eval.h")
+EVAL_LIB_PATH = os.path.join(HERE, "libscsfm_eval.so")
+EVAL_ABI_VERSION = 1  # include/scsfm_eval.h
+_eval = None
+
+
+def get_eval() -> CLib:
+    """The evaluation library, libscsfm_eval.so (singleton): depth evaluation with median scaling
+    (include/scsfm_eval.h).  Built in-tree with hipcc when it is missing or stale, under the same file-lock scheme as
+    ``get()``; raises when that is impossible."""
+    global _eval
+    if _eval is None:
+        with _lock:
+            if _eval is None:
+                from . import build as _build
+                if _build.eval_is_stale():
+                    have = _build.binary_source_id(EVAL_LIB_PATH)
+                    try:
+                        _build.build_eval()
+                    except Exception as e:
+                        raise ScsfmError(f"{EVAL_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(EVAL_LIB_PATH, EVAL_HEADER, EVAL_ABI_VERSION, "scsfm_eval_")
+                if lib.source_id() != _build.eval_source_id():
+                    raise ScsfmError(f"{EVAL_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.eval_source_id()}")
+                _eval = lib
+    return _eval

@@ -1,11 +1,12 @@
-"""Build libscsfm_hip.so and libscsfm_nets.so (gfx950) in-tree with hipcc.
+"""Build libscsfm_hip.so, libscsfm_nets.so and libscsfm_eval.so (gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
 Each shared object is plain HIP + a C ABI (include/scsfm_hip.h: the loss path from csrc/*.hip; include/scsfm_nets.h:
-the depth decoder's fused glue from csrc_nets/*.hip); neither links against torch.  They are written next to this file
-so that they travel with the source tree to the GPU box.  The two are separate targets with separate source ids, so
-that an edit of the nets' kernels leaves the loss library's id (to which recorded PMC counters are tied) unchanged.
+the depth decoder's fused glue from csrc_nets/*.hip; include/scsfm_eval.h: depth evaluation from csrc_eval/*.hip); none
+links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
+are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
+library's id (to which recorded PMC counters are tied) unchanged.
 
 Safe for N processes at once (torchrun: every rank calls ``_lib.get()`` lazily, and ``*.so`` is git-ignored, so a fresh
 clone on an 8-GPU node has no library): the build runs under an exclusive ``flock`` on ``libscsfm_hip.so.lock``, the
@@ -32,6 +33,8 @@ LOG = LIB + ".buildlog"
 INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
 NETS_CSRC = os.path.join(os.path.dirname(HERE), "csrc_nets")
 NETS_LIB = os.path.join(HERE, "libscsfm_nets.so")
+EVAL_CSRC = os.path.join(os.path.dirname(HERE), "csrc_eval")
+EVAL_LIB = os.path.join(HERE, "libscsfm_eval.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -57,6 +60,14 @@ def nets_sources():
 
 def nets_deps():
     return nets_sources() + sorted(glob.glob(os.path.join(NETS_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_nets.h")]
+
+
+def eval_sources():
+    return sorted(glob.glob(os.path.join(EVAL_CSRC, "*.hip")))
+
+
+def eval_deps():
+    return eval_sources() + sorted(glob.glob(os.path.join(EVAL_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_eval.h")]
 
 
 def _hash(files, extra=()):
@@ -90,6 +101,11 @@ def nets_source_id():
     return _hash(nets_deps())
 
 
+def eval_source_id():
+    """source_id() of libscsfm_eval.so: its own sources (csrc_eval/, include/scsfm_eval.h) and the compiler flags."""
+    return _hash(eval_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -111,6 +127,10 @@ def is_stale():
 
 def nets_is_stale():
     return binary_source_id(NETS_LIB) != nets_source_id()
+
+
+def eval_is_stale():
+    return binary_source_id(EVAL_LIB) != eval_source_id()
 
 
 @contextlib.contextmanager
@@ -139,6 +159,11 @@ def build(force=False, verbose=True, extra=()):
 def build_nets(force=False, verbose=True):
     """build() for libscsfm_nets.so: every .hip file under csrc_nets/, against include/scsfm_nets.h."""
     return _build(NETS_LIB, nets_source_id(), nets_sources(), ("-I", INCLUDE), force, verbose)
+
+
+def build_eval(force=False, verbose=True):
+    """build() for libscsfm_eval.so: every .hip file under csrc_eval/, against include/scsfm_eval.h."""
+    return _build(EVAL_LIB, eval_source_id(), eval_sources(), ("-I", INCLUDE), force, verbose)
 
 
 def _build(lib, want, srcs, extra, force, verbose):
@@ -172,5 +197,7 @@ def _build(lib, want, srcs, extra, force, verbose):
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     build_nets(force="--force" in sys.argv)
+    build_eval(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
+    print(EVAL_LIB)
