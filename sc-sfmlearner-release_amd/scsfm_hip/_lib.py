@@ -180,3 +180,33 @@ def get_eval() -> CLib:
                                      f"{_build.eval_source_id()}")
                 _eval = lib
     return _eval
+
+
+ODOM_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_odom.h")
+ODOM_LIB_PATH = os.path.join(HERE, "libscsfm_odom.so")
+ODOM_ABI_VERSION = 1  # include/scsfm_odom.h
+_odom = None
+
+
+def get_odom() -> CLib:
+    """The odometry library, libscsfm_odom.so (singleton): the pose chain of test_vo.py and KITTI odometry evaluation
+    (include/scsfm_odom.h).  Built in-tree with hipcc when it is missing or stale, under the same file-lock scheme as
+    ``get()``; raises when that is impossible."""
+    global _odom
+    if _odom is None:
+        with _lock:
+            if _odom is None:
+                from . import build as _build
+                if _build.odom_is_stale():
+                    have = _build.binary_source_id(ODOM_LIB_PATH)
+                    try:
+                        _build.build_odom()
+                    except Exception as e:
+                        raise ScsfmError(f"{ODOM_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(ODOM_LIB_PATH, ODOM_HEADER, ODOM_ABI_VERSION, "scsfm_odom_")
+                if lib.source_id() != _build.odom_source_id():
+                    raise ScsfmError(f"{ODOM_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.odom_source_id()}")
+                _odom = lib
+    return _odom

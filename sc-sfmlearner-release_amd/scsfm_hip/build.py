@@ -1,10 +1,10 @@
-"""Build libscsfm_hip.so, libscsfm_nets.so and libscsfm_eval.so (gfx950) in-tree with hipcc.
+"""Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so and libscsfm_odom.so (gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
 Each shared object is plain HIP + a C ABI (include/scsfm_hip.h: the loss path from csrc/*.hip; include/scsfm_nets.h:
-the depth decoder's fused glue from csrc_nets/*.hip; include/scsfm_eval.h: depth evaluation from csrc_eval/*.hip); none
-links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
+the depth decoder's fused glue from csrc_nets/*.hip; include/scsfm_eval.h: depth evaluation from csrc_eval/*.hip;
+include/scsfm_odom.h: odometry testing and evaluation from csrc_odom/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
 are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
 library's id (to which recorded PMC counters are tied) unchanged.
 
@@ -35,6 +35,8 @@ NETS_CSRC = os.path.join(os.path.dirname(HERE), "csrc_nets")
 NETS_LIB = os.path.join(HERE, "libscsfm_nets.so")
 EVAL_CSRC = os.path.join(os.path.dirname(HERE), "csrc_eval")
 EVAL_LIB = os.path.join(HERE, "libscsfm_eval.so")
+ODOM_CSRC = os.path.join(os.path.dirname(HERE), "csrc_odom")
+ODOM_LIB = os.path.join(HERE, "libscsfm_odom.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -68,6 +70,14 @@ def eval_sources():
 
 def eval_deps():
     return eval_sources() + sorted(glob.glob(os.path.join(EVAL_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_eval.h")]
+
+
+def odom_sources():
+    return sorted(glob.glob(os.path.join(ODOM_CSRC, "*.hip")))
+
+
+def odom_deps():
+    return odom_sources() + sorted(glob.glob(os.path.join(ODOM_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_odom.h")]
 
 
 def _hash(files, extra=()):
@@ -106,6 +116,11 @@ def eval_source_id():
     return _hash(eval_deps())
 
 
+def odom_source_id():
+    """source_id() of libscsfm_odom.so: its own sources (csrc_odom/, include/scsfm_odom.h) and the compiler flags."""
+    return _hash(odom_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -131,6 +146,10 @@ def nets_is_stale():
 
 def eval_is_stale():
     return binary_source_id(EVAL_LIB) != eval_source_id()
+
+
+def odom_is_stale():
+    return binary_source_id(ODOM_LIB) != odom_source_id()
 
 
 @contextlib.contextmanager
@@ -166,6 +185,11 @@ def build_eval(force=False, verbose=True):
     return _build(EVAL_LIB, eval_source_id(), eval_sources(), ("-I", INCLUDE), force, verbose)
 
 
+def build_odom(force=False, verbose=True):
+    """build() for libscsfm_odom.so: every .hip file under csrc_odom/, against include/scsfm_odom.h."""
+    return _build(ODOM_LIB, odom_source_id(), odom_sources(), ("-I", INCLUDE), force, verbose)
+
+
 def _build(lib, want, srcs, extra, force, verbose):
     if not force and binary_source_id(lib) == want:
         return lib
@@ -198,6 +222,8 @@ if __name__ == "__main__":
     build(force="--force" in sys.argv)
     build_nets(force="--force" in sys.argv)
     build_eval(force="--force" in sys.argv)
+    build_odom(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
     print(EVAL_LIB)
+    print(ODOM_LIB)
