@@ -9,6 +9,40 @@ import torch
 import torch.nn as nn
 
 
+_encoder_ops = None
+
+
+def _E():
+    """scsfm_hip.encoder, imported on first use (a CPU-only run never loads it)"""
+    global _encoder_ops
+    if _encoder_ops is None:
+        from scsfm_hip import encoder
+        _encoder_ops = encoder
+    return _encoder_ops
+
+
+def _fused_applies(x, *bns):
+    """CUDA fp32 contiguous NCHW activations through training-mode BatchNorms take the fused HIP glue
+    (scsfm_hip.encoder); CPU, fp64, channels_last, eval mode and BatchNorms without affine parameters, running
+    statistics or a fixed momentum run the ATen chain unchanged."""
+    return x.is_cuda and _E().applies(x, *bns)
+
+
+def _bn_act(x, bn, act, identity=None):
+    """act(bn(x) [+ identity]), fused when the call qualifies (act is the module's in-place ReLU, or None)"""
+    if _fused_applies(x, bn) and (identity is None or _fused_applies(identity)):
+        return _E().bn_act(x, bn, identity, relu=act is not None)
+    out = bn(x)
+    if identity is not None:
+        out = out + identity
+    return out if act is None else act(out)
+
+
+def _downsample(ds, x):
+    """the down-sample branch nn.Sequential(conv, bn)"""
+    return _bn_act(ds[0](x), ds[1], None)
+
+
 def _conv3x3(cin, cout, stride=1):
     return nn.Conv2d(cin, cout, kernel_size=3, stride=stride, padding=1, bias=False)
 
@@ -26,6 +60,11 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
+        identity = x if self.downsample is None else _downsample(self.downsample, x)
+        out = _bn_act(self.conv1(x), self.bn1, self.relu)
+        return _bn_act(self.conv2(out), self.bn2, self.relu, identity)
+
+    def forward_reference(self, x):
         identity = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
@@ -47,6 +86,12 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
+        identity = x if self.downsample is None else _downsample(self.downsample, x)
+        out = _bn_act(self.conv1(x), self.bn1, self.relu)
+        out = _bn_act(self.conv2(out), self.bn2, self.relu)
+        return _bn_act(self.conv3(out), self.bn3, self.relu, identity)
+
+    def forward_reference(self, x):
         identity = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
@@ -132,11 +177,31 @@ class ResnetEncoder(nn.Module):
             p.requires_grad_(False)
 
     def forward(self, input_image):
+        """The stem's and every block's BatchNorm / ReLU / residual add and the max-pool run as the fused HIP kernels
+        of scsfm_hip.encoder where the call qualifies (``_fused_applies``: CUDA fp32 contiguous NCHW in training mode),
+        through the same modules' parameters and buffers; everything else is ``forward_reference``'s ATen chain."""
         e = self.encoder
-        f0 = e.relu(e.bn1(e.conv1(input_image)))
-        f1 = e.layer1(e.maxpool(f0))
+        f0 = _bn_act(e.conv1(input_image), e.bn1, e.relu)
+        f1 = e.layer1(self._maxpool(f0))
         f2 = e.layer2(f1)
         f3 = e.layer3(f2)
         f4 = e.layer4(f3)
         self.features = [f0, f1, f2, f3, f4]
         return self.features
+
+    def _maxpool(self, f0):
+        e = self.encoder
+        if f0.is_cuda and e.training and _E().pool_applies(f0):
+            return _E().max_pool(f0)
+        return e.maxpool(f0)
+
+    def forward_reference(self, input_image):
+        """forward() by the ATen chain alone, whatever the input (what the fused path is tested against)"""
+        e = self.encoder
+        f0 = e.relu(e.bn1(e.conv1(input_image)))
+        feats, x = [f0], e.maxpool(f0)
+        for layer in (e.layer1, e.layer2, e.layer3, e.layer4):
+            for block in layer:
+                x = block.forward_reference(x)
+            feats.append(x)
+        return feats

@@ -210,3 +210,33 @@ def get_odom() -> CLib:
                                      f"{_build.odom_source_id()}")
                 _odom = lib
     return _odom
+
+
+ENC_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_enc.h")
+ENC_LIB_PATH = os.path.join(HERE, "libscsfm_enc.so")
+ENC_ABI_VERSION = 1  # include/scsfm_enc.h
+_enc = None
+
+
+def get_enc() -> CLib:
+    """The encoder library, libscsfm_enc.so (singleton): the ResNet encoder's fused BatchNorm / ReLU / residual add and
+    max-pool (include/scsfm_enc.h).  Built in-tree with hipcc when it is missing or stale, under the same file-lock
+    scheme as ``get()``; raises when that is impossible."""
+    global _enc
+    if _enc is None:
+        with _lock:
+            if _enc is None:
+                from . import build as _build
+                if _build.enc_is_stale():
+                    have = _build.binary_source_id(ENC_LIB_PATH)
+                    try:
+                        _build.build_enc()
+                    except Exception as e:
+                        raise ScsfmError(f"{ENC_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(ENC_LIB_PATH, ENC_HEADER, ENC_ABI_VERSION, "scsfm_enc_")
+                if lib.source_id() != _build.enc_source_id():
+                    raise ScsfmError(f"{ENC_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.enc_source_id()}")
+                _enc = lib
+    return _enc
