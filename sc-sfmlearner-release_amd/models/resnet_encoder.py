@@ -177,12 +177,18 @@ class ResnetEncoder(nn.Module):
             p.requires_grad_(False)
 
     def forward(self, input_image):
-        """The stem's and every block's BatchNorm / ReLU / residual add and the max-pool run as the fused HIP kernels
-        of scsfm_hip.encoder where the call qualifies (``_fused_applies``: CUDA fp32 contiguous NCHW in training mode),
+        """The stem's BatchNorm / ReLU / max-pool and every block's BatchNorm / ReLU / residual add run as the fused HIP
+        kernels of scsfm_hip.encoder where the call qualifies (``_fused_applies``: CUDA fp32 contiguous NCHW in training mode),
         through the same modules' parameters and buffers; everything else is ``forward_reference``'s ATen chain."""
         e = self.encoder
-        f0 = _bn_act(e.conv1(input_image), e.bn1, e.relu)
-        f1 = e.layer1(self._maxpool(f0))
+        x = e.conv1(input_image)
+        if _fused_applies(x, e.bn1) and _E().pool_applies(x):
+            # the stem: one kernel writes f0 and the pooled map, one backward serves both
+            f0, pooled = _E().bn_act(x, e.bn1, relu=True, pool=True)
+        else:
+            f0 = _bn_act(x, e.bn1, e.relu)
+            pooled = self._maxpool(f0)
+        f1 = e.layer1(pooled)
         f2 = e.layer2(f1)
         f3 = e.layer3(f2)
         f4 = e.layer4(f3)

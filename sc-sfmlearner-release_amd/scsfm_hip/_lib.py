@@ -240,3 +240,33 @@ def get_enc() -> CLib:
                                      f"{_build.enc_source_id()}")
                 _enc = lib
     return _enc
+
+
+STEM_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_stem.h")
+STEM_LIB_PATH = os.path.join(HERE, "libscsfm_stem.so")
+STEM_ABI_VERSION = 1  # include/scsfm_stem.h
+_stem = None
+
+
+def get_stem() -> CLib:
+    """The stem library, libscsfm_stem.so (singleton): the ResNet stem's BatchNorm / ReLU fused with its max-pool
+    (include/scsfm_stem.h).  Built in-tree with hipcc when it is missing or stale, under the same file-lock scheme as
+    ``get()``; raises when that is impossible."""
+    global _stem
+    if _stem is None:
+        with _lock:
+            if _stem is None:
+                from . import build as _build
+                if _build.stem_is_stale():
+                    have = _build.binary_source_id(STEM_LIB_PATH)
+                    try:
+                        _build.build_stem()
+                    except Exception as e:
+                        raise ScsfmError(f"{STEM_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(STEM_LIB_PATH, STEM_HEADER, STEM_ABI_VERSION, "scsfm_stem_")
+                if lib.source_id() != _build.stem_source_id():
+                    raise ScsfmError(f"{STEM_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.stem_source_id()}")
+                _stem = lib
+    return _stem

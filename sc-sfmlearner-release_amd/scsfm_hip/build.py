@@ -1,12 +1,13 @@
-"""Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so and libscsfm_enc.so (gfx950) in-tree with
-hipcc.
+"""Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so and libscsfm_stem.so
+(gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
 Each shared object is plain HIP + a C ABI (include/scsfm_hip.h: the loss path from csrc/*.hip; include/scsfm_nets.h:
 the depth decoder's fused glue from csrc_nets/*.hip; include/scsfm_eval.h: depth evaluation from csrc_eval/*.hip;
 include/scsfm_odom.h: odometry testing and evaluation from csrc_odom/*.hip; include/scsfm_enc.h: the ResNet encoder's
-fused BatchNorm / ReLU / residual / max-pool glue from csrc_enc/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
+fused BatchNorm / ReLU / residual / max-pool glue from csrc_enc/*.hip; include/scsfm_stem.h: the stem's BatchNorm / ReLU
+fused with its max-pool from csrc_stem/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
 are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
 library's id (to which recorded PMC counters are tied) unchanged.
 
@@ -41,6 +42,8 @@ ODOM_CSRC = os.path.join(os.path.dirname(HERE), "csrc_odom")
 ODOM_LIB = os.path.join(HERE, "libscsfm_odom.so")
 ENC_CSRC = os.path.join(os.path.dirname(HERE), "csrc_enc")
 ENC_LIB = os.path.join(HERE, "libscsfm_enc.so")
+STEM_CSRC = os.path.join(os.path.dirname(HERE), "csrc_stem")
+STEM_LIB = os.path.join(HERE, "libscsfm_stem.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -92,6 +95,14 @@ def enc_deps():
     return enc_sources() + sorted(glob.glob(os.path.join(ENC_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_enc.h")]
 
 
+def stem_sources():
+    return sorted(glob.glob(os.path.join(STEM_CSRC, "*.hip")))
+
+
+def stem_deps():
+    return stem_sources() + sorted(glob.glob(os.path.join(STEM_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_stem.h")]
+
+
 def _hash(files, extra=()):
     h = hashlib.sha256()
     for path in files:
@@ -138,6 +149,11 @@ def enc_source_id():
     return _hash(enc_deps())
 
 
+def stem_source_id():
+    """source_id() of libscsfm_stem.so: its own sources (csrc_stem/, include/scsfm_stem.h) and the compiler flags."""
+    return _hash(stem_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -171,6 +187,10 @@ def odom_is_stale():
 
 def enc_is_stale():
     return binary_source_id(ENC_LIB) != enc_source_id()
+
+
+def stem_is_stale():
+    return binary_source_id(STEM_LIB) != stem_source_id()
 
 
 @contextlib.contextmanager
@@ -216,6 +236,11 @@ def build_enc(force=False, verbose=True):
     return _build(ENC_LIB, enc_source_id(), enc_sources(), ("-I", INCLUDE), force, verbose)
 
 
+def build_stem(force=False, verbose=True):
+    """build() for libscsfm_stem.so: every .hip file under csrc_stem/, against include/scsfm_stem.h."""
+    return _build(STEM_LIB, stem_source_id(), stem_sources(), ("-I", INCLUDE), force, verbose)
+
+
 def _build(lib, want, srcs, extra, force, verbose):
     if not force and binary_source_id(lib) == want:
         return lib
@@ -250,8 +275,10 @@ if __name__ == "__main__":
     build_eval(force="--force" in sys.argv)
     build_odom(force="--force" in sys.argv)
     build_enc(force="--force" in sys.argv)
+    build_stem(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
     print(EVAL_LIB)
     print(ODOM_LIB)
     print(ENC_LIB)
+    print(STEM_LIB)

@@ -1,9 +1,11 @@
-"""The ResNet encoder's glue as two autograd functions over libscsfm_enc.so (include/scsfm_enc.h).
+"""The ResNet encoder's glue as autograd functions over libscsfm_enc.so (include/scsfm_enc.h) and, for the stem's
+BatchNorm / ReLU fused with its max-pool, libscsfm_stem.so (include/scsfm_stem.h).
 
     bn_act(x, bn)                      relu(bn(x))                (stem, a block's bn1 / bn2)
     bn_act(x, bn, identity)            relu(bn(x) + identity)     (a block's last BatchNorm)
     bn_act(x, bn, relu=False)          bn(x)                      (the down-sample branch)
-    max_pool(x)                        nn.MaxPool2d(3, 2, 1)(x)   (the stem)
+    max_pool(x)                        nn.MaxPool2d(3, 2, 1)(x)
+    bn_act(x, bn, pool=True)           (f0, max_pool(f0)) with f0 = relu(bn(x)), one read of x       (the stem)
 
 ``bn`` is an ``nn.BatchNorm2d`` in training mode: its batch statistics normalise, its running statistics and batch
 counter are updated in place once per call (by the kernel -- no separate launches), and its parameters get their
@@ -122,13 +124,71 @@ class _MaxPool(torch.autograd.Function):
         return dx
 
 
-def bn_act(x, bn, identity=None, relu=True):
-    """Train-mode ``bn(x)``, plus ``identity`` and through a ReLU as asked (an identity implies the ReLU)."""
+class _BnReluPool(torch.autograd.Function):
+    """(f0, pooled) = (relu(bn(x)), max_pool(f0)).  A gradient that does not arrive stays None (the pose encoder's f0
+    has no reader): the backward then runs the kernel variant that reads nothing for it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn):
+        lib = _lib.get_stem()
+        B, C, H, W = x.shape
+        PH, PW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        f0 = torch.empty_like(x)
+        out = torch.empty((B, C, PH, PW), dtype=x.dtype, device=x.device)
+        arg = torch.empty((B, C, PH, PW), dtype=torch.uint8, device=x.device)
+        stat = torch.empty((3, C), dtype=torch.float32, device=x.device)
+        n = lib.size("scsfm_stem_workspace_bytes", B, C, H, W)
+        ws = torch.empty(n // 8, dtype=torch.float64, device=x.device)
+        lib.call("scsfm_stem_fwd_f32", B, C, H, W, float(bn.eps), float(bn.momentum), x.data_ptr(), weight.data_ptr(),
+                 bias.data_ptr(), f0.data_ptr(), out.data_ptr(), arg.data_ptr(), stat.data_ptr(),
+                 bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr(),
+                 ws.data_ptr(), n, _stream(x))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, weight, bias, stat, arg)
+        return f0, out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_f0, g_pool):
+        if g_f0 is None and g_pool is None:
+            return None, None, None, None
+        x, weight, bias, stat, arg = ctx.saved_tensors
+        B, C, H, W = x.shape
+        dx = torch.empty_like(x)
+        dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+        dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
+        if g_f0 is not None:
+            g_f0 = g_f0.contiguous()
+        if g_pool is None:
+            # nothing read the pooled map: what is left is the backward of relu(bn(x)) alone
+            lib = _lib.get_enc()
+            ws, n = _workspace(lib, x)
+            lib.call("scsfm_enc_bn_bwd_f32", B, C, H, W, 1, g_f0.data_ptr(), x.data_ptr(), 0, weight.data_ptr(),
+                     bias.data_ptr(), stat.data_ptr(), dx.data_ptr(), 0, dgamma.data_ptr(), dbeta.data_ptr(),
+                     ws.data_ptr(), n, _stream(x))
+            return dx, dgamma, dbeta, None
+        lib = _lib.get_stem()
+        g_pool = g_pool.contiguous()
+        n = lib.size("scsfm_stem_workspace_bytes", B, C, H, W)
+        ws = torch.empty(n // 8, dtype=torch.float64, device=x.device)
+        lib.call("scsfm_stem_bwd_f32", B, C, H, W, g_pool.data_ptr(), 0 if g_f0 is None else g_f0.data_ptr(),
+                 arg.data_ptr(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), stat.data_ptr(), dx.data_ptr(),
+                 dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), n, _stream(x))
+        return dx, dgamma, dbeta, None
+
+
+def bn_act(x, bn, identity=None, relu=True, pool=False):
+    """Train-mode ``bn(x)``, plus ``identity`` and through a ReLU as asked (an identity implies the ReLU).  With
+    ``pool=True`` (the stem: ReLU, no identity) -> ``(f0, max_pool(f0))`` from one fused forward and backward."""
     if not applies(x, bn):
         raise ValueError("scsfm_hip.encoder.bn_act: CUDA fp32 contiguous NCHW input and a training-mode affine "
                          f"BatchNorm2d with running statistics only (got {x.device} {x.dtype} {tuple(x.shape)})")
     if identity is not None and not relu:
         raise ValueError("bn_act: the residual form ends in a ReLU")
+    if pool:
+        if identity is not None or not relu:
+            raise ValueError("bn_act: pool=True is relu(bn(x)) followed by the max-pool, without an identity")
+        return _BnReluPool.apply(x, bn.weight, bn.bias, bn)
     mode = 2 if identity is not None else (1 if relu else 0)
     return _BnAct.apply(x, identity, bn.weight, bn.bias, bn, mode)
 
