@@ -270,3 +270,33 @@ def get_stem() -> CLib:
                                      f"{_build.stem_source_id()}")
                 _stem = lib
     return _stem
+
+
+SNIP_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_snip.h")
+SNIP_LIB_PATH = os.path.join(HERE, "libscsfm_snip.so")
+SNIP_ABI_VERSION = 1  # include/scsfm_snip.h
+_snip = None
+
+
+def get_snip() -> CLib:
+    """The snippet library, libscsfm_snip.so (singleton): test_pose.py's 5-frame snippet pose evaluation
+    (include/scsfm_snip.h).  Built in-tree with hipcc when it is missing or stale, under the same file-lock scheme as
+    ``get()``; raises when that is impossible."""
+    global _snip
+    if _snip is None:
+        with _lock:
+            if _snip is None:
+                from . import build as _build
+                if _build.snip_is_stale():
+                    have = _build.binary_source_id(SNIP_LIB_PATH)
+                    try:
+                        _build.build_snip()
+                    except Exception as e:
+                        raise ScsfmError(f"{SNIP_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(SNIP_LIB_PATH, SNIP_HEADER, SNIP_ABI_VERSION, "scsfm_snip_")
+                if lib.source_id() != _build.snip_source_id():
+                    raise ScsfmError(f"{SNIP_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.snip_source_id()}")
+                _snip = lib
+    return _snip

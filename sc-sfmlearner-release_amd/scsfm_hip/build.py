@@ -1,5 +1,5 @@
-"""Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so and libscsfm_stem.so
-(gfx950) in-tree with hipcc.
+"""Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so, libscsfm_stem.so and
+libscsfm_snip.so (gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
@@ -7,7 +7,8 @@ Each shared object is plain HIP + a C ABI (include/scsfm_hip.h: the loss path fr
 the depth decoder's fused glue from csrc_nets/*.hip; include/scsfm_eval.h: depth evaluation from csrc_eval/*.hip;
 include/scsfm_odom.h: odometry testing and evaluation from csrc_odom/*.hip; include/scsfm_enc.h: the ResNet encoder's
 fused BatchNorm / ReLU / residual / max-pool glue from csrc_enc/*.hip; include/scsfm_stem.h: the stem's BatchNorm / ReLU
-fused with its max-pool from csrc_stem/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
+fused with its max-pool from csrc_stem/*.hip; include/scsfm_snip.h: the 5-frame snippet pose evaluation from
+csrc_snip/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
 are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
 library's id (to which recorded PMC counters are tied) unchanged.
 
@@ -44,6 +45,8 @@ ENC_CSRC = os.path.join(os.path.dirname(HERE), "csrc_enc")
 ENC_LIB = os.path.join(HERE, "libscsfm_enc.so")
 STEM_CSRC = os.path.join(os.path.dirname(HERE), "csrc_stem")
 STEM_LIB = os.path.join(HERE, "libscsfm_stem.so")
+SNIP_CSRC = os.path.join(os.path.dirname(HERE), "csrc_snip")
+SNIP_LIB = os.path.join(HERE, "libscsfm_snip.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -103,6 +106,14 @@ def stem_deps():
     return stem_sources() + sorted(glob.glob(os.path.join(STEM_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_stem.h")]
 
 
+def snip_sources():
+    return sorted(glob.glob(os.path.join(SNIP_CSRC, "*.hip")))
+
+
+def snip_deps():
+    return snip_sources() + sorted(glob.glob(os.path.join(SNIP_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_snip.h")]
+
+
 def _hash(files, extra=()):
     h = hashlib.sha256()
     for path in files:
@@ -154,6 +165,11 @@ def stem_source_id():
     return _hash(stem_deps())
 
 
+def snip_source_id():
+    """source_id() of libscsfm_snip.so: its own sources (csrc_snip/, include/scsfm_snip.h) and the compiler flags."""
+    return _hash(snip_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -191,6 +207,10 @@ def enc_is_stale():
 
 def stem_is_stale():
     return binary_source_id(STEM_LIB) != stem_source_id()
+
+
+def snip_is_stale():
+    return binary_source_id(SNIP_LIB) != snip_source_id()
 
 
 @contextlib.contextmanager
@@ -241,6 +261,11 @@ def build_stem(force=False, verbose=True):
     return _build(STEM_LIB, stem_source_id(), stem_sources(), ("-I", INCLUDE), force, verbose)
 
 
+def build_snip(force=False, verbose=True):
+    """build() for libscsfm_snip.so: every .hip file under csrc_snip/, against include/scsfm_snip.h."""
+    return _build(SNIP_LIB, snip_source_id(), snip_sources(), ("-I", INCLUDE), force, verbose)
+
+
 def _build(lib, want, srcs, extra, force, verbose):
     if not force and binary_source_id(lib) == want:
         return lib
@@ -276,9 +301,11 @@ if __name__ == "__main__":
     build_odom(force="--force" in sys.argv)
     build_enc(force="--force" in sys.argv)
     build_stem(force="--force" in sys.argv)
+    build_snip(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
     print(EVAL_LIB)
     print(ODOM_LIB)
     print(ENC_LIB)
     print(STEM_LIB)
+    print(SNIP_LIB)
