@@ -300,3 +300,33 @@ def get_snip() -> CLib:
                                      f"{_build.snip_source_id()}")
                 _snip = lib
     return _snip
+
+
+PREP_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_prep.h")
+PREP_LIB_PATH = os.path.join(HERE, "libscsfm_prep.so")
+PREP_ABI_VERSION = 1  # include/scsfm_prep.h
+_prep = None
+
+
+def get_prep() -> CLib:
+    """The preparation library, libscsfm_prep.so (singleton): the resize and the Velodyne depth maps of
+    data/prepare_train_data.py (include/scsfm_prep.h).  Built in-tree with hipcc when it is missing or stale, under the
+    same file-lock scheme as ``get()``; raises when that is impossible."""
+    global _prep
+    if _prep is None:
+        with _lock:
+            if _prep is None:
+                from . import build as _build
+                if _build.prep_is_stale():
+                    have = _build.binary_source_id(PREP_LIB_PATH)
+                    try:
+                        _build.build_prep()
+                    except Exception as e:
+                        raise ScsfmError(f"{PREP_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(PREP_LIB_PATH, PREP_HEADER, PREP_ABI_VERSION, "scsfm_prep_")
+                if lib.source_id() != _build.prep_source_id():
+                    raise ScsfmError(f"{PREP_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.prep_source_id()}")
+                _prep = lib
+    return _prep

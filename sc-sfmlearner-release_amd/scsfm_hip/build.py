@@ -1,5 +1,5 @@
-"""Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so, libscsfm_stem.so and
-libscsfm_snip.so (gfx950) in-tree with hipcc.
+"""Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so, libscsfm_stem.so,
+libscsfm_snip.so and libscsfm_prep.so (gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
@@ -8,7 +8,8 @@ the depth decoder's fused glue from csrc_nets/*.hip; include/scsfm_eval.h: depth
 include/scsfm_odom.h: odometry testing and evaluation from csrc_odom/*.hip; include/scsfm_enc.h: the ResNet encoder's
 fused BatchNorm / ReLU / residual / max-pool glue from csrc_enc/*.hip; include/scsfm_stem.h: the stem's BatchNorm / ReLU
 fused with its max-pool from csrc_stem/*.hip; include/scsfm_snip.h: the 5-frame snippet pose evaluation from
-csrc_snip/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
+csrc_snip/*.hip; include/scsfm_prep.h: the resize and the Velodyne depth maps of data/prepare_train_data.py from
+csrc_prep/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
 are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
 library's id (to which recorded PMC counters are tied) unchanged.
 
@@ -47,6 +48,8 @@ STEM_CSRC = os.path.join(os.path.dirname(HERE), "csrc_stem")
 STEM_LIB = os.path.join(HERE, "libscsfm_stem.so")
 SNIP_CSRC = os.path.join(os.path.dirname(HERE), "csrc_snip")
 SNIP_LIB = os.path.join(HERE, "libscsfm_snip.so")
+PREP_CSRC = os.path.join(os.path.dirname(HERE), "csrc_prep")
+PREP_LIB = os.path.join(HERE, "libscsfm_prep.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -114,6 +117,14 @@ def snip_deps():
     return snip_sources() + sorted(glob.glob(os.path.join(SNIP_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_snip.h")]
 
 
+def prep_sources():
+    return sorted(glob.glob(os.path.join(PREP_CSRC, "*.hip")))
+
+
+def prep_deps():
+    return prep_sources() + sorted(glob.glob(os.path.join(PREP_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_prep.h")]
+
+
 def _hash(files, extra=()):
     h = hashlib.sha256()
     for path in files:
@@ -170,6 +181,11 @@ def snip_source_id():
     return _hash(snip_deps())
 
 
+def prep_source_id():
+    """source_id() of libscsfm_prep.so: its own sources (csrc_prep/, include/scsfm_prep.h) and the compiler flags."""
+    return _hash(prep_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -211,6 +227,10 @@ def stem_is_stale():
 
 def snip_is_stale():
     return binary_source_id(SNIP_LIB) != snip_source_id()
+
+
+def prep_is_stale():
+    return binary_source_id(PREP_LIB) != prep_source_id()
 
 
 @contextlib.contextmanager
@@ -266,6 +286,11 @@ def build_snip(force=False, verbose=True):
     return _build(SNIP_LIB, snip_source_id(), snip_sources(), ("-I", INCLUDE), force, verbose)
 
 
+def build_prep(force=False, verbose=True):
+    """build() for libscsfm_prep.so: every .hip file under csrc_prep/, against include/scsfm_prep.h."""
+    return _build(PREP_LIB, prep_source_id(), prep_sources(), ("-I", INCLUDE), force, verbose)
+
+
 def _build(lib, want, srcs, extra, force, verbose):
     if not force and binary_source_id(lib) == want:
         return lib
@@ -302,6 +327,7 @@ if __name__ == "__main__":
     build_enc(force="--force" in sys.argv)
     build_stem(force="--force" in sys.argv)
     build_snip(force="--force" in sys.argv)
+    build_prep(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
     print(EVAL_LIB)
@@ -309,3 +335,4 @@ if __name__ == "__main__":
     print(ENC_LIB)
     print(STEM_LIB)
     print(SNIP_LIB)
+    print(PREP_LIB)
