@@ -330,3 +330,33 @@ def get_prep() -> CLib:
                                      f"{_build.prep_source_id()}")
                 _prep = lib
     return _prep
+
+
+VIS_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_vis.h")
+VIS_LIB_PATH = os.path.join(HERE, "libscsfm_vis.so")
+VIS_ABI_VERSION = 1  # include/scsfm_vis.h
+_vis = None
+
+
+def get_vis() -> CLib:
+    """The visualisation library, libscsfm_vis.so (singleton): the input normalisation, the per-image maximum and the
+    colour-mapped pictures of run_inference.py (include/scsfm_vis.h).  Built in-tree with hipcc when it is missing or
+    stale, under the same file-lock scheme as ``get()``; raises when that is impossible."""
+    global _vis
+    if _vis is None:
+        with _lock:
+            if _vis is None:
+                from . import build as _build
+                if _build.vis_is_stale():
+                    have = _build.binary_source_id(VIS_LIB_PATH)
+                    try:
+                        _build.build_vis()
+                    except Exception as e:
+                        raise ScsfmError(f"{VIS_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(VIS_LIB_PATH, VIS_HEADER, VIS_ABI_VERSION, "scsfm_vis_")
+                if lib.source_id() != _build.vis_source_id():
+                    raise ScsfmError(f"{VIS_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.vis_source_id()}")
+                _vis = lib
+    return _vis

@@ -1,5 +1,5 @@
 """Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so, libscsfm_stem.so,
-libscsfm_snip.so and libscsfm_prep.so (gfx950) in-tree with hipcc.
+libscsfm_snip.so, libscsfm_prep.so and libscsfm_vis.so (gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
@@ -9,7 +9,8 @@ include/scsfm_odom.h: odometry testing and evaluation from csrc_odom/*.hip; incl
 fused BatchNorm / ReLU / residual / max-pool glue from csrc_enc/*.hip; include/scsfm_stem.h: the stem's BatchNorm / ReLU
 fused with its max-pool from csrc_stem/*.hip; include/scsfm_snip.h: the 5-frame snippet pose evaluation from
 csrc_snip/*.hip; include/scsfm_prep.h: the resize and the Velodyne depth maps of data/prepare_train_data.py from
-csrc_prep/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
+csrc_prep/*.hip; include/scsfm_vis.h: the input normalisation, the per-image maximum and the colour-mapped pictures of
+run_inference.py from csrc_vis/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
 are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
 library's id (to which recorded PMC counters are tied) unchanged.
 
@@ -50,6 +51,8 @@ SNIP_CSRC = os.path.join(os.path.dirname(HERE), "csrc_snip")
 SNIP_LIB = os.path.join(HERE, "libscsfm_snip.so")
 PREP_CSRC = os.path.join(os.path.dirname(HERE), "csrc_prep")
 PREP_LIB = os.path.join(HERE, "libscsfm_prep.so")
+VIS_CSRC = os.path.join(os.path.dirname(HERE), "csrc_vis")
+VIS_LIB = os.path.join(HERE, "libscsfm_vis.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -125,6 +128,14 @@ def prep_deps():
     return prep_sources() + sorted(glob.glob(os.path.join(PREP_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_prep.h")]
 
 
+def vis_sources():
+    return sorted(glob.glob(os.path.join(VIS_CSRC, "*.hip")))
+
+
+def vis_deps():
+    return vis_sources() + sorted(glob.glob(os.path.join(VIS_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_vis.h")]
+
+
 def _hash(files, extra=()):
     h = hashlib.sha256()
     for path in files:
@@ -186,6 +197,11 @@ def prep_source_id():
     return _hash(prep_deps())
 
 
+def vis_source_id():
+    """source_id() of libscsfm_vis.so: its own sources (csrc_vis/, include/scsfm_vis.h) and the compiler flags."""
+    return _hash(vis_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -231,6 +247,10 @@ def snip_is_stale():
 
 def prep_is_stale():
     return binary_source_id(PREP_LIB) != prep_source_id()
+
+
+def vis_is_stale():
+    return binary_source_id(VIS_LIB) != vis_source_id()
 
 
 @contextlib.contextmanager
@@ -291,6 +311,11 @@ def build_prep(force=False, verbose=True):
     return _build(PREP_LIB, prep_source_id(), prep_sources(), ("-I", INCLUDE), force, verbose)
 
 
+def build_vis(force=False, verbose=True):
+    """build() for libscsfm_vis.so: every .hip file under csrc_vis/, against include/scsfm_vis.h."""
+    return _build(VIS_LIB, vis_source_id(), vis_sources(), ("-I", INCLUDE), force, verbose)
+
+
 def _build(lib, want, srcs, extra, force, verbose):
     if not force and binary_source_id(lib) == want:
         return lib
@@ -328,6 +353,7 @@ if __name__ == "__main__":
     build_stem(force="--force" in sys.argv)
     build_snip(force="--force" in sys.argv)
     build_prep(force="--force" in sys.argv)
+    build_vis(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
     print(EVAL_LIB)
@@ -336,3 +362,4 @@ if __name__ == "__main__":
     print(STEM_LIB)
     print(SNIP_LIB)
     print(PREP_LIB)
+    print(VIS_LIB)
