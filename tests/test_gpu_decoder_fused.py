@@ -4,12 +4,16 @@ DispResNet, fused against DepthDecoder.forward_reference on the same CUDA tensor
 
 Forward values are bit-identical.  Backward values are bit-identical except where a reflection-pad corner sums four
 padded-gradient entries (ATen adds them with atomics in no fixed order): those entries are bounded by the rounding of
-a reordered sum of their terms."""
+a reordered sum of their terms.  The odd shapes include those around the kernels' 256-element chunk, and each op also
+runs a fill of which 40 % are special values (zeros of both signs, infinities, NaN, denormals, saturating and huge
+magnitudes: tests/_decoder_ref.py)."""
+import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import _decoder_ref as R
 from _util import report
 
 pytestmark = pytest.mark.gpu
@@ -22,8 +26,9 @@ U = 2.0 ** -24  # unit roundoff of fp32
 LEVELS_UP = [(12, 256, 256, 8, 26), (12, 128, 128, 16, 52), (12, 64, 64, 32, 104), (12, 32, 64, 64, 208),
              (12, 16, 0, 128, 416)]
 LEVELS_PAD = [(12, 256, 16, 52), (12, 128, 32, 104), (12, 64, 64, 208), (12, 32, 128, 416), (12, 16, 256, 832)]
-ODD_UP = [(1, 3, 2, 1, 1), (1, 5, 0, 2, 3), (2, 7, 3, 3, 5), (1, 4, 4, 5, 131)]
-ODD_PAD = [(1, 3, 2, 2), (2, 5, 3, 3), (1, 4, 7, 5), (3, 2, 5, 263)]
+ODD_UP = R.ODD_UP + R.CHUNK_UP
+ODD_PAD = R.ODD_PAD + R.CHUNK_PAD
+FLT_MAX = float(np.finfo(np.float32).max)
 
 
 def bits(t):
@@ -122,6 +127,87 @@ def test_pad_matches_aten(shape, elu):
 def test_up_cat_pad_matches_aten(shape):
     worst = run_up(*shape, seed=sum(shape))
     report(f"decoder up_cat_pad {shape}: corner entries at {worst:.3f} of their bound")
+
+
+def same_bits_nan(name, got, ref):
+    """the same NaN positions, the same bits elsewhere"""
+    assert got.shape == ref.shape, name
+    nan = torch.isnan(ref)
+    assert torch.equal(torch.isnan(got), nan), f"{name}: NaN positions"
+    assert same_bits(got[~nan], ref[~nan]), f"{name}: bits"
+
+
+def finite_part(gp):
+    return torch.where(torch.isfinite(gp), gp, torch.zeros_like(gp))
+
+
+def check_grad_special(name, got, ref, mask, term_abs, finite_abs):
+    """check_grad for gradients that hold special values; term_abs / finite_abs: the sum of |terms| behind each entry,
+    over all terms / over the finite ones.  Outside `mask`: the same NaN positions and bits.  Inside it (four or more
+    terms, added by ATen in no fixed order): where every term is finite the rounding bound of check_grad; where a term
+    is infinite or NaN the same class (NaN, +inf, -inf or finite).  Entries whose finite terms can overflow in one
+    order and not in another (their sum of |terms| exceeds FLT_MAX) are left out of both."""
+    same_bits_nan(name + " outside the corner entries", got[~mask], ref[~mask])
+    g, r, t, no_overflow = got[mask].double(), ref[mask].double(), term_abs[mask], finite_abs[mask] <= FLT_MAX
+    tame = torch.isfinite(t) & no_overflow
+    d = (g[tame] - r[tame]).abs()
+    bound = 8 * U * t[tame] + 1e-45
+    assert bool((d <= bound).all()), f"{name}: corner entries off by {float((d / bound).max()):.2f} x the bound"
+    wild = ~torch.isfinite(t) & no_overflow
+    for cls in (torch.isnan, torch.isposinf, torch.isneginf):
+        assert torch.equal(cls(g[wild]), cls(r[wild])), f"{name}: {cls.__name__} at the corner entries"
+    return int(tame.sum()), int(wild.sum())
+
+
+def _special(shape, rng):
+    return torch.from_numpy(R.fill(shape, "special", rng)).to(DEV)
+
+
+@pytest.mark.parametrize("shape", [(2, 5, 3, 3), (1, 1, 2, 257), (3, 2, 5, 263), (2, 8, 16, 52)])
+@pytest.mark.parametrize("elu", [False, True])
+def test_pad_matches_aten_on_special_values(shape, elu):
+    """Measured on an MI355X: ATen and the kernels agree bit for bit on every entry outside the corners, denormal
+    g * (r + 1) and expm1f at each of R.SPECIALS included (neither side flushes denormals), here and for up_cat_pad."""
+    from scsfm_hip import decoder as D
+    B, C, H, W = shape
+    rng = np.random.default_rng(sum(shape) + elu)
+    x0, gp = _special(shape, rng), _special((B, C, H + 2, W + 2), rng)
+    x1, x2 = x0.clone().requires_grad_(), x0.clone().requires_grad_()
+    out = (D.elu_pad if elu else D.pad)(x1)
+    ref = aten_pad_elu(x2, elu)
+    same_bits_nan("forward", out, ref)
+    out.backward(gp)
+    ref.backward(gp)
+    n = check_grad_special("g_x", x1.grad, x2.grad, many_terms(C, H, W, x0).expand(x0.shape), fold_abs(gp),
+                           fold_abs(finite_part(gp)))
+    report(f"decoder pad elu={int(elu)} {shape} special values: as ATen ({n[0]} bounded, {n[1]} classed corner entries)")
+
+
+@pytest.mark.parametrize("shape", [(1, 3, 2, 1, 1), (2, 7, 3, 3, 5), (1, 2, 0, 2, 129), (1, 4, 4, 5, 131),
+                                   (2, 16, 8, 16, 52)])
+def test_up_cat_pad_matches_aten_on_special_values(shape):
+    from scsfm_hip import decoder as D
+    B, Ca, Cs, H, W = shape
+    rng = np.random.default_rng(sum(shape))
+    a0 = _special((B, Ca, H, W), rng)
+    s0 = _special((B, Cs, 2 * H, 2 * W), rng) if Cs else None
+    gp = _special((B, Ca + Cs, 2 * H + 2, 2 * W + 2), rng)
+    a1, a2 = a0.clone().requires_grad_(), a0.clone().requires_grad_()
+    s1 = s0.clone().requires_grad_() if Cs else None
+    s2 = s0.clone().requires_grad_() if Cs else None
+    out = D.up_cat_pad(a1, s1)
+    ref = aten_up_cat_pad(a2, s2)
+    same_bits_nan("forward", out, ref)
+    out.backward(gp)
+    ref.backward(gp)
+    terms_a = F.avg_pool2d(fold_abs(gp[:, :Ca]), 2) * 4
+    mask_a = F.max_pool2d(many_terms(Ca, 2 * H, 2 * W, a0).double(), 2) > 0
+    n = check_grad_special("g_a", a1.grad, a2.grad, mask_a.expand(a0.shape), terms_a,
+                           F.avg_pool2d(fold_abs(finite_part(gp[:, :Ca])), 2) * 4)
+    if Cs:
+        check_grad_special("g_skip", s1.grad, s2.grad, many_terms(Cs, 2 * H, 2 * W, s0).expand(s0.shape),
+                           fold_abs(gp[:, Ca:]), fold_abs(finite_part(gp[:, Ca:])))
+    report(f"decoder up_cat_pad {shape} special values: as ATen ({n[0]} bounded, {n[1]} classed corner entries of g_a)")
 
 
 def test_upsample_backward_sums_children_row_major_from_zero():
