@@ -360,3 +360,33 @@ def get_vis() -> CLib:
                                      f"{_build.vis_source_id()}")
                 _vis = lib
     return _vis
+
+
+DVIS_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_dvis.h")
+DVIS_LIB_PATH = os.path.join(HERE, "libscsfm_dvis.so")
+DVIS_ABI_VERSION = 1  # include/scsfm_dvis.h
+_dvis = None
+
+
+def get_dvis() -> CLib:
+    """The depth visualisation library, libscsfm_dvis.so (singleton): the scaled prediction at the ground truth's size,
+    the colour range and the magma pictures of eval_depth.py --vis_dir (include/scsfm_dvis.h).  Built in-tree with hipcc
+    when it is missing or stale, under the same file-lock scheme as ``get()``; raises when that is impossible."""
+    global _dvis
+    if _dvis is None:
+        with _lock:
+            if _dvis is None:
+                from . import build as _build
+                if _build.dvis_is_stale():
+                    have = _build.binary_source_id(DVIS_LIB_PATH)
+                    try:
+                        _build.build_dvis()
+                    except Exception as e:
+                        raise ScsfmError(f"{DVIS_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(DVIS_LIB_PATH, DVIS_HEADER, DVIS_ABI_VERSION, "scsfm_dvis_")
+                if lib.source_id() != _build.dvis_source_id():
+                    raise ScsfmError(f"{DVIS_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.dvis_source_id()}")
+                _dvis = lib
+    return _dvis
