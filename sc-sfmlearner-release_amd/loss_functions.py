@@ -22,7 +22,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from inverse_warp import inverse_warp, inverse_warp2  # noqa: F401  (re-exported like the reference, :5)
-from scsfm_hip import capi, ops
+from scsfm_hip import capi, config, ops, validation
 
 device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
 
@@ -151,8 +151,18 @@ def compute_total_loss(tgt_img, ref_imgs, intrinsics, tgt_depth, ref_depths, pos
 @torch.no_grad()
 def compute_errors(gt, pred, dataset):
     """loss_functions.py:162-205 -> [abs_diff, abs_rel, sq_rel, a1, a2, a3] (Python floats, batch
-    means).  Validation-only; boolean-mask gathers and per-image medians stay on PyTorch device ops
-    (SURVEY.md §8 a11), the six metric sums are accumulated on the device and read back once."""
+    means).  Validation-only.  fp32 tensors on a HIP device go through libscsfm_val.so
+    (scsfm_hip/validation.py: one call per batch, one read-back); anything else -- CPU tensors, other
+    dtypes, or config.errors_on_torch() -- takes the torch body below."""
+    if (gt.is_cuda and pred.device == gt.device and gt.dtype == torch.float32 and pred.dtype == torch.float32
+            and not config.errors_on_torch()):
+        return validation.batch_mean(validation.depth_errors(gt, pred, dataset))
+    return _compute_errors_torch(gt, pred, dataset)
+
+
+def _compute_errors_torch(gt, pred, dataset):
+    """compute_errors on PyTorch ops: boolean-mask gathers and per-image medians, the six metric sums
+    accumulated on the device and read back once."""
     batch_size, h, w = gt.size()
     if dataset == 'kitti':  # Garg/Eigen crop
         y1, y2 = int(0.40810811 * h), int(0.99189189 * h)

@@ -25,7 +25,8 @@ LIB_PATH = os.environ.get("SCSFM_HIP_LIB") or os.path.join(HERE, "libscsfm_hip.s
 
 ABI_VERSION = 9  # include/scsfm_hip.h
 
-_CTYPES = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "size_t": ctypes.c_size_t, "double": ctypes.c_double}
+_CTYPES = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "size_t": ctypes.c_size_t, "double": ctypes.c_double,
+           "float": ctypes.c_float}
 _DECL = re.compile(r"^(int|size_t)\s+(scsfm_\w+)\s*\(([^)]*)\)\s*;", re.M | re.S)
 
 
@@ -390,3 +391,33 @@ def get_dvis() -> CLib:
                                      f"{_build.dvis_source_id()}")
                 _dvis = lib
     return _dvis
+
+
+VAL_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_val.h")
+VAL_LIB_PATH = os.path.join(HERE, "libscsfm_val.so")
+VAL_ABI_VERSION = 1  # include/scsfm_val.h
+_val = None
+
+
+def get_val() -> CLib:
+    """The validation library, libscsfm_val.so (singleton): the ground-truth validation metrics of train.py --with-gt
+    (include/scsfm_val.h).  Built in-tree with hipcc when it is missing or stale, under the same file-lock scheme as
+    ``get()``; raises when that is impossible."""
+    global _val
+    if _val is None:
+        with _lock:
+            if _val is None:
+                from . import build as _build
+                if _build.val_is_stale():
+                    have = _build.binary_source_id(VAL_LIB_PATH)
+                    try:
+                        _build.build_val()
+                    except Exception as e:
+                        raise ScsfmError(f"{VAL_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(VAL_LIB_PATH, VAL_HEADER, VAL_ABI_VERSION, "scsfm_val_")
+                if lib.source_id() != _build.val_source_id():
+                    raise ScsfmError(f"{VAL_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.val_source_id()}")
+                _val = lib
+    return _val

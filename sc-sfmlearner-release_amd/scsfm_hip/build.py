@@ -1,5 +1,5 @@
 """Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so, libscsfm_stem.so,
-libscsfm_snip.so, libscsfm_prep.so, libscsfm_vis.so and libscsfm_dvis.so (gfx950) in-tree with hipcc.
+libscsfm_snip.so, libscsfm_prep.so, libscsfm_vis.so, libscsfm_dvis.so and libscsfm_val.so (gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
@@ -11,7 +11,8 @@ fused with its max-pool from csrc_stem/*.hip; include/scsfm_snip.h: the 5-frame 
 csrc_snip/*.hip; include/scsfm_prep.h: the resize and the Velodyne depth maps of data/prepare_train_data.py from
 csrc_prep/*.hip; include/scsfm_vis.h: the input normalisation, the per-image maximum and the colour-mapped pictures of
 run_inference.py from csrc_vis/*.hip; include/scsfm_dvis.h: the scaled prediction, the colour range and the magma
-pictures of eval_depth.py --vis_dir from csrc_dvis/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
+pictures of eval_depth.py --vis_dir from csrc_dvis/*.hip; include/scsfm_val.h: the ground-truth validation metrics of
+train.py --with-gt from csrc_val/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
 are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
 library's id (to which recorded PMC counters are tied) unchanged.
 
@@ -56,6 +57,8 @@ VIS_CSRC = os.path.join(os.path.dirname(HERE), "csrc_vis")
 VIS_LIB = os.path.join(HERE, "libscsfm_vis.so")
 DVIS_CSRC = os.path.join(os.path.dirname(HERE), "csrc_dvis")
 DVIS_LIB = os.path.join(HERE, "libscsfm_dvis.so")
+VAL_CSRC = os.path.join(os.path.dirname(HERE), "csrc_val")
+VAL_LIB = os.path.join(HERE, "libscsfm_val.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -147,6 +150,14 @@ def dvis_deps():
     return dvis_sources() + sorted(glob.glob(os.path.join(DVIS_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_dvis.h")]
 
 
+def val_sources():
+    return sorted(glob.glob(os.path.join(VAL_CSRC, "*.hip")))
+
+
+def val_deps():
+    return val_sources() + sorted(glob.glob(os.path.join(VAL_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_val.h")]
+
+
 def _hash(files, extra=()):
     h = hashlib.sha256()
     for path in files:
@@ -218,6 +229,11 @@ def dvis_source_id():
     return _hash(dvis_deps())
 
 
+def val_source_id():
+    """source_id() of libscsfm_val.so: its own sources (csrc_val/, include/scsfm_val.h) and the compiler flags."""
+    return _hash(val_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -271,6 +287,10 @@ def vis_is_stale():
 
 def dvis_is_stale():
     return binary_source_id(DVIS_LIB) != dvis_source_id()
+
+
+def val_is_stale():
+    return binary_source_id(VAL_LIB) != val_source_id()
 
 
 @contextlib.contextmanager
@@ -341,6 +361,11 @@ def build_dvis(force=False, verbose=True):
     return _build(DVIS_LIB, dvis_source_id(), dvis_sources(), ("-I", INCLUDE), force, verbose)
 
 
+def build_val(force=False, verbose=True):
+    """build() for libscsfm_val.so: every .hip file under csrc_val/, against include/scsfm_val.h."""
+    return _build(VAL_LIB, val_source_id(), val_sources(), ("-I", INCLUDE), force, verbose)
+
+
 def _build(lib, want, srcs, extra, force, verbose):
     if not force and binary_source_id(lib) == want:
         return lib
@@ -380,6 +405,7 @@ if __name__ == "__main__":
     build_prep(force="--force" in sys.argv)
     build_vis(force="--force" in sys.argv)
     build_dvis(force="--force" in sys.argv)
+    build_val(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
     print(EVAL_LIB)
@@ -390,3 +416,4 @@ if __name__ == "__main__":
     print(PREP_LIB)
     print(VIS_LIB)
     print(DVIS_LIB)
+    print(VAL_LIB)

@@ -72,3 +72,23 @@ def smooth_rides_along():
 def set_smooth_rides_along(on):
     global _smooth_rides
     _smooth_rides = bool(on)
+
+
+_errors_torch = None
+
+
+def errors_on_torch():
+    """Does loss_functions.compute_errors run its torch body (a Python loop over the batch: mask gathers, torch.median,
+    some thirty small launches per image) also for fp32 tensors on a HIP device, instead of libscsfm_val.so?  Default
+    off; SCSFM_ERRORS_TORCH=1 (read once) or set_errors_on_torch(True) force it (tools/bench_validation_errors.py's
+    A/B)."""
+    global _errors_torch
+    if _errors_torch is None:
+        import os
+        _errors_torch = os.environ.get("SCSFM_ERRORS_TORCH", "0") == "1"
+    return _errors_torch
+
+
+def set_errors_on_torch(on):
+    global _errors_torch
+    _errors_torch = bool(on)

@@ -39,6 +39,7 @@ except ImportError:
     compute_total_loss = None
 from scsfm_hip import config as hip_config
 from scsfm_hip import dist as hip_dist
+from scsfm_hip import validation as hip_validation
 from utils import save_checkpoint
 
 parser = argparse.ArgumentParser(description='Structure from Motion Learner training on KITTI and CityScapes Dataset',
@@ -453,11 +454,8 @@ def validate_with_gt(args, val_loader, disp_net, epoch, logger, output_writers=[
         if depth.nelement() == 0:
             continue
         output_disp = disp_net(tgt_img)
-        output_depth = 1 / output_disp[:, 0]
-        if depth.nelement() != output_depth.nelement():
-            b, h, w = depth.size()
-            output_depth = torch.nn.functional.interpolate(output_depth.unsqueeze(1), [h, w]).squeeze(1)
-        errors.update(compute_errors(depth, output_depth, args.dataset))
+        # 1 / disp, the nearest resize to the ground truth's size and compute_errors' per-image loop: one library call
+        errors.update(hip_validation.batch_mean(hip_validation.depth_errors(depth, output_disp, args.dataset, is_disp=True)))
         batch_time.update(time.time() - end)
         end = time.time()
         logger.valid_bar.update(i + 1)
