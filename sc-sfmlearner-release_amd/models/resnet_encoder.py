@@ -21,17 +21,39 @@ def _E():
     return _encoder_ops
 
 
+_encoder_eval_ops = None
+
+
+def _EV():
+    """scsfm_hip.encoder_eval, imported on first use (a CPU-only run never loads it)"""
+    global _encoder_eval_ops
+    if _encoder_eval_ops is None:
+        from scsfm_hip import encoder_eval
+        _encoder_eval_ops = encoder_eval
+    return _encoder_eval_ops
+
+
 def _fused_applies(x, *bns):
     """CUDA fp32 contiguous NCHW activations through training-mode BatchNorms take the fused HIP glue
-    (scsfm_hip.encoder); CPU, fp64, channels_last, eval mode and BatchNorms without affine parameters, running
-    statistics or a fixed momentum run the ATen chain unchanged."""
+    (scsfm_hip.encoder); eval mode is ``_eval_applies``'s; CPU, fp64, channels_last and BatchNorms without affine
+    parameters, running statistics or a fixed momentum run the ATen chain unchanged."""
     return x.is_cuda and _E().applies(x, *bns)
 
 
+def _eval_applies(x, *bns):
+    """CUDA fp32 contiguous NCHW activations through eval-mode BatchNorms with grad mode off take the fused eval-mode HIP
+    glue (scsfm_hip.encoder_eval); eval mode with grad enabled, SCSFM_EVAL_TORCH=1, CPU, fp64, channels_last and
+    BatchNorms without affine parameters or running statistics run the ATen chain unchanged."""
+    return x.is_cuda and _EV().applies(x, *bns)
+
+
 def _bn_act(x, bn, act, identity=None):
-    """act(bn(x) [+ identity]), fused when the call qualifies (act is the module's in-place ReLU, or None)"""
+    """act(bn(x) [+ identity]), fused when the call qualifies (act is the module's in-place ReLU, or None): by
+    scsfm_hip.encoder in training mode, else by scsfm_hip.encoder_eval in eval mode under no_grad, else ATen"""
     if _fused_applies(x, bn) and (identity is None or _fused_applies(identity)):
         return _E().bn_act(x, bn, identity, relu=act is not None)
+    if _eval_applies(x, bn) and (identity is None or _eval_applies(identity)):
+        return _EV().bn_act(x, bn, identity, relu=act is not None)
     out = bn(x)
     if identity is not None:
         out = out + identity
@@ -179,12 +201,16 @@ class ResnetEncoder(nn.Module):
     def forward(self, input_image):
         """The stem's BatchNorm / ReLU / max-pool and every block's BatchNorm / ReLU / residual add run as the fused HIP
         kernels of scsfm_hip.encoder where the call qualifies (``_fused_applies``: CUDA fp32 contiguous NCHW in training mode),
-        through the same modules' parameters and buffers; everything else is ``forward_reference``'s ATen chain."""
+        or of scsfm_hip.encoder_eval (``_eval_applies``: the same tensors in eval mode with grad mode off), through the same
+        modules' parameters and buffers; everything else is ``forward_reference``'s ATen chain."""
         e = self.encoder
         x = e.conv1(input_image)
         if _fused_applies(x, e.bn1) and _E().pool_applies(x):
             # the stem: one kernel writes f0 and the pooled map, one backward serves both
             f0, pooled = _E().bn_act(x, e.bn1, relu=True, pool=True)
+        elif _eval_applies(x, e.bn1) and _EV().pool_applies(x):
+            # ... and in eval mode one kernel without a backward
+            f0, pooled = _EV().bn_act(x, e.bn1, relu=True, pool=True)
         else:
             f0 = _bn_act(x, e.bn1, e.relu)
             pooled = self._maxpool(f0)
@@ -199,6 +225,8 @@ class ResnetEncoder(nn.Module):
         e = self.encoder
         if f0.is_cuda and e.training and _E().pool_applies(f0):
             return _E().max_pool(f0)
+        if f0.is_cuda and not e.training and _EV().pool_applies(f0):
+            return _EV().max_pool(f0)
         return e.maxpool(f0)
 
     def forward_reference(self, input_image):

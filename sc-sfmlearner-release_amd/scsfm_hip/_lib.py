@@ -421,3 +421,33 @@ def get_val() -> CLib:
                                      f"{_build.val_source_id()}")
                 _val = lib
     return _val
+
+
+ENCEVAL_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_enceval.h")
+ENCEVAL_LIB_PATH = os.path.join(HERE, "libscsfm_enceval.so")
+ENCEVAL_ABI_VERSION = 1  # include/scsfm_enceval.h
+_enceval = None
+
+
+def get_enceval() -> CLib:
+    """The eval-mode encoder library, libscsfm_enceval.so (singleton): the ResNet encoder's BatchNorm from the running
+    statistics fused with the ReLU / residual add, and the stem's max-pool (include/scsfm_enceval.h).  Built in-tree with
+    hipcc when it is missing or stale, under the same file-lock scheme as ``get()``; raises when that is impossible."""
+    global _enceval
+    if _enceval is None:
+        with _lock:
+            if _enceval is None:
+                from . import build as _build
+                if _build.enceval_is_stale():
+                    have = _build.binary_source_id(ENCEVAL_LIB_PATH)
+                    try:
+                        _build.build_enceval()
+                    except Exception as e:
+                        raise ScsfmError(f"{ENCEVAL_LIB_PATH} is stale or missing ({have}) and cannot be built here: "
+                                         f"{e}") from e
+                lib = CLib(ENCEVAL_LIB_PATH, ENCEVAL_HEADER, ENCEVAL_ABI_VERSION, "scsfm_enceval_")
+                if lib.source_id() != _build.enceval_source_id():
+                    raise ScsfmError(f"{ENCEVAL_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.enceval_source_id()}")
+                _enceval = lib
+    return _enceval

@@ -1,5 +1,6 @@
 """Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so, libscsfm_stem.so,
-libscsfm_snip.so, libscsfm_prep.so, libscsfm_vis.so, libscsfm_dvis.so and libscsfm_val.so (gfx950) in-tree with hipcc.
+libscsfm_snip.so, libscsfm_prep.so, libscsfm_vis.so, libscsfm_dvis.so, libscsfm_val.so and libscsfm_enceval.so (gfx950)
+in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
@@ -12,7 +13,8 @@ csrc_snip/*.hip; include/scsfm_prep.h: the resize and the Velodyne depth maps of
 csrc_prep/*.hip; include/scsfm_vis.h: the input normalisation, the per-image maximum and the colour-mapped pictures of
 run_inference.py from csrc_vis/*.hip; include/scsfm_dvis.h: the scaled prediction, the colour range and the magma
 pictures of eval_depth.py --vis_dir from csrc_dvis/*.hip; include/scsfm_val.h: the ground-truth validation metrics of
-train.py --with-gt from csrc_val/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
+train.py --with-gt from csrc_val/*.hip; include/scsfm_enceval.h: the ResNet encoder's eval-mode BatchNorm / ReLU / residual /
+max-pool glue from csrc_enceval/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
 are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
 library's id (to which recorded PMC counters are tied) unchanged.
 
@@ -59,6 +61,8 @@ DVIS_CSRC = os.path.join(os.path.dirname(HERE), "csrc_dvis")
 DVIS_LIB = os.path.join(HERE, "libscsfm_dvis.so")
 VAL_CSRC = os.path.join(os.path.dirname(HERE), "csrc_val")
 VAL_LIB = os.path.join(HERE, "libscsfm_val.so")
+ENCEVAL_CSRC = os.path.join(os.path.dirname(HERE), "csrc_enceval")
+ENCEVAL_LIB = os.path.join(HERE, "libscsfm_enceval.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -158,6 +162,15 @@ def val_deps():
     return val_sources() + sorted(glob.glob(os.path.join(VAL_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_val.h")]
 
 
+def enceval_sources():
+    return sorted(glob.glob(os.path.join(ENCEVAL_CSRC, "*.hip")))
+
+
+def enceval_deps():
+    return enceval_sources() + sorted(glob.glob(os.path.join(ENCEVAL_CSRC, "*.h"))) + \
+        [os.path.join(INCLUDE, "scsfm_enceval.h")]
+
+
 def _hash(files, extra=()):
     h = hashlib.sha256()
     for path in files:
@@ -234,6 +247,11 @@ def val_source_id():
     return _hash(val_deps())
 
 
+def enceval_source_id():
+    """source_id() of libscsfm_enceval.so: its own sources (csrc_enceval/, include/scsfm_enceval.h) and the flags."""
+    return _hash(enceval_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -291,6 +309,10 @@ def dvis_is_stale():
 
 def val_is_stale():
     return binary_source_id(VAL_LIB) != val_source_id()
+
+
+def enceval_is_stale():
+    return binary_source_id(ENCEVAL_LIB) != enceval_source_id()
 
 
 @contextlib.contextmanager
@@ -366,6 +388,11 @@ def build_val(force=False, verbose=True):
     return _build(VAL_LIB, val_source_id(), val_sources(), ("-I", INCLUDE), force, verbose)
 
 
+def build_enceval(force=False, verbose=True):
+    """build() for libscsfm_enceval.so: every .hip file under csrc_enceval/, against include/scsfm_enceval.h."""
+    return _build(ENCEVAL_LIB, enceval_source_id(), enceval_sources(), ("-I", INCLUDE), force, verbose)
+
+
 def _build(lib, want, srcs, extra, force, verbose):
     if not force and binary_source_id(lib) == want:
         return lib
@@ -406,6 +433,7 @@ if __name__ == "__main__":
     build_vis(force="--force" in sys.argv)
     build_dvis(force="--force" in sys.argv)
     build_val(force="--force" in sys.argv)
+    build_enceval(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
     print(EVAL_LIB)
@@ -417,3 +445,4 @@ if __name__ == "__main__":
     print(VIS_LIB)
     print(DVIS_LIB)
     print(VAL_LIB)
+    print(ENCEVAL_LIB)
