@@ -56,8 +56,20 @@ class DepthDecoder(nn.Module):
 
     def forward(self, feats):
         if self.fused_path_applies(feats):
+            if self.bias_path_applies():
+                return self.forward_fused_bias(feats)
             return self.forward_fused(feats)
         return self.forward_reference(feats)
+
+    def bias_path_applies(self):
+        """On the fused path, the biases of the convolutions are folded into the glue behind them (forward_fused_bias)
+        when every one of them is a contiguous CUDA fp32 tensor, unless SCSFM_DECODER_BIAS=0 (scsfm_hip.config) selects
+        forward_fused."""
+        from scsfm_hip import config
+        if not config.decoder_bias_folded():
+            return False
+        biases = [self._conv(k).bias for k in range(len(self.decoder))]
+        return all(b is not None and b.is_cuda and b.dtype == torch.float32 and b.is_contiguous() for b in biases)
 
     def fused_path_applies(self, feats):
         """CUDA fp32 contiguous NCHW features and weights take the fused HIP glue (forward_fused); CPU, fp64 and
@@ -102,6 +114,33 @@ class DepthDecoder(nn.Module):
             x = D.elu_pad(b)
             if i in self._head:
                 outputs.append(self.alpha * self.sigmoid(conv(self._head[i], x)) + self.beta)
+        return outputs[::-1]
+
+    def forward_fused_bias(self, feats):
+        """forward_fused with every convolution called without its bias, which the glue that follows adds in front of
+        its ELU (scsfm_hip.decoder_bias.up_cat_pad / elu_pad) or of the head's sigmoid (disp_head), and whose gradient
+        that glue's backward sums: ATen's broadcast add after each convolution and its grad_output.sum((0, 2, 3)) no
+        longer run as passes of their own.  Conv (0, 1) without a head at scale 0 has no glue behind it and keeps its
+        module call."""
+        from scsfm_hip import decoder as D, decoder_bias as DB
+
+        def conv(k, x):
+            m = self._conv(k)
+            return F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups), m.bias
+
+        outputs = []
+        x = D.pad(feats[-1])
+        for i in range(4, -1, -1):
+            a, bias = conv(self._up[(i, 0)], x)
+            x = DB.up_cat_pad(a, bias, feats[i - 1] if self.use_skips and i > 0 else None)
+            if i == 0 and i not in self._head:
+                self._conv(self._up[(i, 1)])(x)
+                break
+            b, bias = conv(self._up[(i, 1)], x)
+            x = DB.elu_pad(b, bias)
+            if i in self._head:
+                h, bias = conv(self._head[i], x)
+                outputs.append(DB.disp_head(h, bias, self.alpha, self.beta))
         return outputs[::-1]
 
 

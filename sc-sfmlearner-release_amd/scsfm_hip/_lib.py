@@ -451,3 +451,33 @@ def get_enceval() -> CLib:
                                      f"{_build.enceval_source_id()}")
                 _enceval = lib
     return _enceval
+
+
+DECB_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_decb.h")
+DECB_LIB_PATH = os.path.join(HERE, "libscsfm_decb.so")
+DECB_ABI_VERSION = 1  # include/scsfm_decb.h
+_decb = None
+
+
+def get_decb() -> CLib:
+    """The decoder-bias library, libscsfm_decb.so (singleton): the depth decoder's fused glue with the biases of its
+    convolutions folded in (include/scsfm_decb.h).  Built in-tree with hipcc when it is missing or stale, under the same
+    file-lock scheme as ``get()``; raises when that is impossible."""
+    global _decb
+    if _decb is None:
+        with _lock:
+            if _decb is None:
+                from . import build as _build
+                if _build.decb_is_stale():
+                    have = _build.binary_source_id(DECB_LIB_PATH)
+                    try:
+                        _build.build_decb()
+                    except Exception as e:
+                        raise ScsfmError(f"{DECB_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(DECB_LIB_PATH, DECB_HEADER, DECB_ABI_VERSION, "scsfm_decb_")
+                if lib.source_id() != _build.decb_source_id():
+                    raise ScsfmError(f"{DECB_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.decb_source_id()}")
+                _decb = lib
+    return _decb

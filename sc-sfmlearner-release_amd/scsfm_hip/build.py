@@ -1,6 +1,6 @@
 """Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so, libscsfm_stem.so,
-libscsfm_snip.so, libscsfm_prep.so, libscsfm_vis.so, libscsfm_dvis.so, libscsfm_val.so and libscsfm_enceval.so (gfx950)
-in-tree with hipcc.
+libscsfm_snip.so, libscsfm_prep.so, libscsfm_vis.so, libscsfm_dvis.so, libscsfm_val.so, libscsfm_enceval.so and
+libscsfm_decb.so (gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
@@ -14,7 +14,8 @@ csrc_prep/*.hip; include/scsfm_vis.h: the input normalisation, the per-image max
 run_inference.py from csrc_vis/*.hip; include/scsfm_dvis.h: the scaled prediction, the colour range and the magma
 pictures of eval_depth.py --vis_dir from csrc_dvis/*.hip; include/scsfm_val.h: the ground-truth validation metrics of
 train.py --with-gt from csrc_val/*.hip; include/scsfm_enceval.h: the ResNet encoder's eval-mode BatchNorm / ReLU / residual /
-max-pool glue from csrc_enceval/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
+max-pool glue from csrc_enceval/*.hip; include/scsfm_decb.h: the depth decoder's glue with the convolutions' biases folded
+in from csrc_decb/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
 are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
 library's id (to which recorded PMC counters are tied) unchanged.
 
@@ -63,6 +64,8 @@ VAL_CSRC = os.path.join(os.path.dirname(HERE), "csrc_val")
 VAL_LIB = os.path.join(HERE, "libscsfm_val.so")
 ENCEVAL_CSRC = os.path.join(os.path.dirname(HERE), "csrc_enceval")
 ENCEVAL_LIB = os.path.join(HERE, "libscsfm_enceval.so")
+DECB_CSRC = os.path.join(os.path.dirname(HERE), "csrc_decb")
+DECB_LIB = os.path.join(HERE, "libscsfm_decb.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -171,6 +174,14 @@ def enceval_deps():
         [os.path.join(INCLUDE, "scsfm_enceval.h")]
 
 
+def decb_sources():
+    return sorted(glob.glob(os.path.join(DECB_CSRC, "*.hip")))
+
+
+def decb_deps():
+    return decb_sources() + sorted(glob.glob(os.path.join(DECB_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_decb.h")]
+
+
 def _hash(files, extra=()):
     h = hashlib.sha256()
     for path in files:
@@ -252,6 +263,11 @@ def enceval_source_id():
     return _hash(enceval_deps())
 
 
+def decb_source_id():
+    """source_id() of libscsfm_decb.so: its own sources (csrc_decb/, include/scsfm_decb.h) and the compiler flags."""
+    return _hash(decb_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -313,6 +329,10 @@ def val_is_stale():
 
 def enceval_is_stale():
     return binary_source_id(ENCEVAL_LIB) != enceval_source_id()
+
+
+def decb_is_stale():
+    return binary_source_id(DECB_LIB) != decb_source_id()
 
 
 @contextlib.contextmanager
@@ -393,6 +413,11 @@ def build_enceval(force=False, verbose=True):
     return _build(ENCEVAL_LIB, enceval_source_id(), enceval_sources(), ("-I", INCLUDE), force, verbose)
 
 
+def build_decb(force=False, verbose=True):
+    """build() for libscsfm_decb.so: every .hip file under csrc_decb/, against include/scsfm_decb.h."""
+    return _build(DECB_LIB, decb_source_id(), decb_sources(), ("-I", INCLUDE), force, verbose)
+
+
 def _build(lib, want, srcs, extra, force, verbose):
     if not force and binary_source_id(lib) == want:
         return lib
@@ -434,6 +459,7 @@ if __name__ == "__main__":
     build_dvis(force="--force" in sys.argv)
     build_val(force="--force" in sys.argv)
     build_enceval(force="--force" in sys.argv)
+    build_decb(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
     print(EVAL_LIB)
@@ -446,3 +472,4 @@ if __name__ == "__main__":
     print(DVIS_LIB)
     print(VAL_LIB)
     print(ENCEVAL_LIB)
+    print(DECB_LIB)

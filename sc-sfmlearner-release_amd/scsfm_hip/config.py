@@ -92,3 +92,23 @@ def errors_on_torch():
 def set_errors_on_torch(on):
     global _errors_torch
     _errors_torch = bool(on)
+
+
+_decoder_bias = None
+
+
+def decoder_bias_folded():
+    """Does DepthDecoder.forward call its convolutions without their biases and hand these to the fused glue that
+    follows (libscsfm_decb.so: forward_fused_bias), instead of letting ATen add and reduce them in passes of their own
+    (forward_fused)?  Default on; SCSFM_DECODER_BIAS=0 (read once) or set_decoder_bias_folded(False) select
+    forward_fused."""
+    global _decoder_bias
+    if _decoder_bias is None:
+        import os
+        _decoder_bias = os.environ.get("SCSFM_DECODER_BIAS", "1") != "0"
+    return _decoder_bias
+
+
+def set_decoder_bias_folded(on):
+    global _decoder_bias
+    _decoder_bias = None if on is None else bool(on)
