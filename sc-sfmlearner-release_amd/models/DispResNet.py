@@ -101,8 +101,15 @@ class DepthDecoder(nn.Module):
         scsfm_hip.decoder: the same modules' convolutions (``Conv3x3.conv``, ``_conv``) receive the same padded tensors, bit for
         bit.  Per level i: a = conv (i,0)(P), P = R(cat[U(E(a)), f_{i-1}]), b = conv (i,1)(P), Q = R(E(b)); Q is
         the input of both conv (i-1,0) and head i (the reference pads E(b) once for each)."""
-        from scsfm_hip import decoder as D
-        conv = lambda k, x: self._conv(k)(x)  # noqa: E731
+        from scsfm_hip import conv_wrw as CW, decoder as D
+
+        def conv(k, x):
+            m = self._conv(k)
+            if CW.applies(x, m):  # (the weight gradient from libscsfm_wrw.so; the bias as ATen adds it)
+                y = CW.conv3x3_valid(x, m.weight)
+                return y if m.bias is None else y + m.bias.view(1, -1, 1, 1)
+            return m(x)
+
         outputs = []
         x = D.pad(feats[-1])
         for i in range(4, -1, -1):
@@ -120,12 +127,15 @@ class DepthDecoder(nn.Module):
         """forward_fused with every convolution called without its bias, which the glue that follows adds in front of
         its ELU (scsfm_hip.decoder_bias.up_cat_pad / elu_pad) or of the head's sigmoid (disp_head), and whose gradient
         that glue's backward sums: ATen's broadcast add after each convolution and its grad_output.sum((0, 2, 3)) no
-        longer run as passes of their own.  Conv (0, 1) without a head at scale 0 has no glue behind it and keeps its
+        longer run as passes of their own.  The low-channel convolutions that scsfm_hip.conv_wrw routes take their weight
+        gradient from libscsfm_wrw.so (SCSFM_DECODER_WRW=0: MIOpen's, as every other layer).  Conv (0, 1) without a head at scale 0 has no glue behind it and keeps its
         module call."""
-        from scsfm_hip import decoder as D, decoder_bias as DB
+        from scsfm_hip import conv_wrw as CW, decoder as D, decoder_bias as DB
 
         def conv(k, x):
             m = self._conv(k)
+            if CW.applies(x, m):  # (the weight gradient from libscsfm_wrw.so)
+                return CW.conv3x3_valid(x, m.weight), m.bias
             return F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups), m.bias
 
         outputs = []

@@ -481,3 +481,33 @@ def get_decb() -> CLib:
                                      f"{_build.decb_source_id()}")
                 _decb = lib
     return _decb
+
+
+WRW_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_wrw.h")
+WRW_LIB_PATH = os.path.join(HERE, "libscsfm_wrw.so")
+WRW_ABI_VERSION = 1  # include/scsfm_wrw.h
+_wrw = None
+
+
+def get_wrw() -> CLib:
+    """The weight-gradient library, libscsfm_wrw.so (singleton): the weight gradient of the depth decoder's low-channel
+    3x3 convolutions on the fp32 matrix instruction (include/scsfm_wrw.h).  Built in-tree with hipcc when it is missing
+    or stale, under the same file-lock scheme as ``get()``; raises when that is impossible."""
+    global _wrw
+    if _wrw is None:
+        with _lock:
+            if _wrw is None:
+                from . import build as _build
+                if _build.wrw_is_stale():
+                    have = _build.binary_source_id(WRW_LIB_PATH)
+                    try:
+                        _build.build_wrw()
+                    except Exception as e:
+                        raise ScsfmError(f"{WRW_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(WRW_LIB_PATH, WRW_HEADER, WRW_ABI_VERSION, "scsfm_wrw_")
+                if lib.source_id() != _build.wrw_source_id():
+                    raise ScsfmError(f"{WRW_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.wrw_source_id()}")
+                _wrw = lib
+    return _wrw

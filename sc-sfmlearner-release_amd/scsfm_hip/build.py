@@ -1,6 +1,6 @@
 """Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so, libscsfm_stem.so,
-libscsfm_snip.so, libscsfm_prep.so, libscsfm_vis.so, libscsfm_dvis.so, libscsfm_val.so, libscsfm_enceval.so and
-libscsfm_decb.so (gfx950) in-tree with hipcc.
+libscsfm_snip.so, libscsfm_prep.so, libscsfm_vis.so, libscsfm_dvis.so, libscsfm_val.so, libscsfm_enceval.so,
+libscsfm_decb.so and libscsfm_wrw.so (gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
@@ -15,7 +15,8 @@ run_inference.py from csrc_vis/*.hip; include/scsfm_dvis.h: the scaled predictio
 pictures of eval_depth.py --vis_dir from csrc_dvis/*.hip; include/scsfm_val.h: the ground-truth validation metrics of
 train.py --with-gt from csrc_val/*.hip; include/scsfm_enceval.h: the ResNet encoder's eval-mode BatchNorm / ReLU / residual /
 max-pool glue from csrc_enceval/*.hip; include/scsfm_decb.h: the depth decoder's glue with the convolutions' biases folded
-in from csrc_decb/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
+in from csrc_decb/*.hip; include/scsfm_wrw.h: the weight gradient of the depth decoder's low-channel convolutions from
+csrc_wrw/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
 are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
 library's id (to which recorded PMC counters are tied) unchanged.
 
@@ -66,6 +67,8 @@ ENCEVAL_CSRC = os.path.join(os.path.dirname(HERE), "csrc_enceval")
 ENCEVAL_LIB = os.path.join(HERE, "libscsfm_enceval.so")
 DECB_CSRC = os.path.join(os.path.dirname(HERE), "csrc_decb")
 DECB_LIB = os.path.join(HERE, "libscsfm_decb.so")
+WRW_CSRC = os.path.join(os.path.dirname(HERE), "csrc_wrw")
+WRW_LIB = os.path.join(HERE, "libscsfm_wrw.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -182,6 +185,14 @@ def decb_deps():
     return decb_sources() + sorted(glob.glob(os.path.join(DECB_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_decb.h")]
 
 
+def wrw_sources():
+    return sorted(glob.glob(os.path.join(WRW_CSRC, "*.hip")))
+
+
+def wrw_deps():
+    return wrw_sources() + sorted(glob.glob(os.path.join(WRW_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_wrw.h")]
+
+
 def _hash(files, extra=()):
     h = hashlib.sha256()
     for path in files:
@@ -268,6 +279,11 @@ def decb_source_id():
     return _hash(decb_deps())
 
 
+def wrw_source_id():
+    """source_id() of libscsfm_wrw.so: its own sources (csrc_wrw/, include/scsfm_wrw.h) and the compiler flags."""
+    return _hash(wrw_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -333,6 +349,10 @@ def enceval_is_stale():
 
 def decb_is_stale():
     return binary_source_id(DECB_LIB) != decb_source_id()
+
+
+def wrw_is_stale():
+    return binary_source_id(WRW_LIB) != wrw_source_id()
 
 
 @contextlib.contextmanager
@@ -418,6 +438,11 @@ def build_decb(force=False, verbose=True):
     return _build(DECB_LIB, decb_source_id(), decb_sources(), ("-I", INCLUDE), force, verbose)
 
 
+def build_wrw(force=False, verbose=True):
+    """build() for libscsfm_wrw.so: every .hip file under csrc_wrw/, against include/scsfm_wrw.h."""
+    return _build(WRW_LIB, wrw_source_id(), wrw_sources(), ("-I", INCLUDE), force, verbose)
+
+
 def _build(lib, want, srcs, extra, force, verbose):
     if not force and binary_source_id(lib) == want:
         return lib
@@ -460,6 +485,7 @@ if __name__ == "__main__":
     build_val(force="--force" in sys.argv)
     build_enceval(force="--force" in sys.argv)
     build_decb(force="--force" in sys.argv)
+    build_wrw(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
     print(EVAL_LIB)
@@ -473,3 +499,4 @@ if __name__ == "__main__":
     print(VAL_LIB)
     print(ENCEVAL_LIB)
     print(DECB_LIB)
+    print(WRW_LIB)

@@ -112,3 +112,22 @@ def decoder_bias_folded():
 def set_decoder_bias_folded(on):
     global _decoder_bias
     _decoder_bias = None if on is None else bool(on)
+
+
+_decoder_wrw = None
+
+
+def decoder_wrw():
+    """Do the depth decoder's low-channel 3x3 convolutions take their weight gradient from libscsfm_wrw.so
+    (scsfm_hip.conv_wrw.conv3x3_valid) instead of MIOpen's weight-gradient path?  Default on; SCSFM_DECODER_WRW=0 (read
+    once) or set_decoder_wrw(False) restore the plain convolution calls."""
+    global _decoder_wrw
+    if _decoder_wrw is None:
+        import os
+        _decoder_wrw = os.environ.get("SCSFM_DECODER_WRW", "1") != "0"
+    return _decoder_wrw
+
+
+def set_decoder_wrw(on):
+    global _decoder_wrw
+    _decoder_wrw = None if on is None else bool(on)

@@ -1,0 +1,194 @@
+"""Every distinct convolution problem of DispResNet(18) and PoseResNet(18) at configs[1] (batch 12, 256 x 832, fp32, the
+fused paths), alone: which kernels MIOpen launches for its weight gradient, its data gradient and its forward, how long
+they take, and what the shape allows.
+
+    rocprofv3 --kernel-trace -d <dir> -o trace -- python tools/conv_layers_bench.py --iters 10 --out <dir>/segments.json
+    python tools/conv_layers_bench.py --report <dir>/trace_results.db --segments <dir>/segments.json
+
+The first form collects the problems (a dispatch mode records every aten.convolution of one training-mode forward of
+each net, with the module that owns the weight) and launches, per problem, aten.convolution_backward with the output mask
+[False, True, False] (weight only), with [True, False, False] (input only) and the forward, `--iters` times each after 3
+warm-up calls; for the problems scsfm_hip.conv_wrw covers it also launches libscsfm_wrw.so's weight gradient.  Each
+timed stretch lies between two marker kernels (erfinv in front, digamma behind: nothing else here launches them), so
+the report can tell which kernels belong to it.  The second form reads the trace and prints one row per problem and
+direction: launches per step of the training loop (3 DispResNet passes, 4 PoseResNet passes), the kernels of one call
+(convolution, transposes, casts, zero-fill) with their launches per call and median durations, their sum, the FLOPs
+and the bytes the operands hold, and the two floors: FLOPs / 157 TFLOP/s (the fp32 matrix peak) and bytes / 6.29 TB/s
+(the measured copy rate)."""
+import argparse
+import json
+import os
+import re
+import sqlite3
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "sc-sfmlearner-release_amd"))
+sys.path.insert(0, ROOT)
+
+COPY_RATE = 6.29e12    # bytes/s, the measured copy rate of one MI355X
+MATRIX_PEAK = 157.3e12  # fp32 FLOP/s of v_mfma_f32_*_f32
+B, H, W = 12, 256, 832
+PASSES = {"disp": 3, "pose": 4}  # per training step with two reference frames
+DIRECTIONS = ("wrw", "bwd", "fwd", "wrw_hip")
+
+
+def collect():
+    """-> [problem dict] of both nets: distinct (x shape, w shape, stride, padding, dilation, groups), with the names of
+    the modules that own the weights and the calls per pass"""
+    import torch
+    from torch.utils._python_dispatch import TorchDispatchMode
+
+    import models
+
+    class Recorder(TorchDispatchMode):
+        def __init__(self, owner):
+            super().__init__()
+            self.owner, self.calls = owner, []
+
+        def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+            if func is torch.ops.aten.convolution.default:
+                x, w, bias, stride, padding, dilation, transposed, _, groups = args[:9]
+                assert not transposed
+                self.calls.append((tuple(x.shape), tuple(w.shape), tuple(stride), tuple(padding), tuple(dilation),
+                                   int(groups), self.owner.get(w.data_ptr(), "?")))
+            return func(*args, **(kwargs or {}))
+
+    torch.manual_seed(0)
+    problems = {}
+    for net_name, make, inputs in (("disp", lambda: models.DispResNet(18, False), 1),
+                                   ("pose", lambda: models.PoseResNet(18, False), 2)):
+        net = make().cuda().train()
+        owner = {m.weight.data_ptr(): name for name, m in net.named_modules() if isinstance(m, torch.nn.Conv2d)}
+        imgs = [torch.randn(B, 3, H, W, device="cuda") for _ in range(inputs)]
+        with Recorder(owner) as rec:
+            net(*imgs)
+        for xs, ws, st, pd, dl, gr, name in rec.calls:
+            key = (xs, ws, st, pd, dl, gr)
+            p = problems.setdefault(key, {"x": xs, "w": ws, "stride": st, "padding": pd, "dilation": dl, "groups": gr,
+                                          "layers": [], "per_step": 0})
+            p["layers"].append(f"{net_name}.{name}")
+            p["per_step"] += PASSES[net_name]
+        del net, imgs
+        torch.cuda.empty_cache()
+    return list(problems.values())
+
+
+def out_shape(p):
+    (b, _, h, w), (co, _, kh, kw) = p["x"], p["w"]
+    ho = (h + 2 * p["padding"][0] - p["dilation"][0] * (kh - 1) - 1) // p["stride"][0] + 1
+    wo = (w + 2 * p["padding"][1] - p["dilation"][1] * (kw - 1) - 1) // p["stride"][1] + 1
+    return (b, co, ho, wo)
+
+
+def run(iters, out):
+    import torch
+
+    from bench import MIOPEN_SOLVERS_NEVER_CHOSEN
+    for k in MIOPEN_SOLVERS_NEVER_CHOSEN:  # (the search space of bench.py's runs)
+        os.environ.setdefault(k, "0")
+    from scsfm_hip import conv_wrw as CW
+    problems = collect()
+    marker = torch.rand(64, device="cuda") * 0.5
+    segments = []
+    for pi, p in enumerate(problems):
+        x = torch.randn(*p["x"], device="cuda")
+        w = torch.randn(*p["w"], device="cuda")
+        gy = torch.randn(*out_shape(p), device="cuda")
+        conv = (list(p["stride"]), list(p["padding"]), list(p["dilation"]), False, [0, 0], p["groups"])
+
+        def backward(mask):
+            return torch.ops.aten.convolution_backward(gy, x, w, None, *conv, mask)
+
+        calls = {"wrw": lambda: backward([False, True, False]), "bwd": lambda: backward([True, False, False]),
+                 "fwd": lambda: torch.ops.aten.convolution(x, w, None, *conv)}
+        plain3x3 = p["w"][2:] == (3, 3) and p["stride"] == (1, 1) and p["padding"] == (0, 0) and p["groups"] == 1
+        if plain3x3 and CW.covers(p["w"][1], p["w"][0]):
+            calls["wrw_hip"] = lambda: CW.weight_grad(x, gy)
+        for d in DIRECTIONS:
+            if d not in calls:
+                continue
+            for _ in range(3):
+                calls[d]()
+            torch.cuda.synchronize()
+            torch.erfinv(marker)
+            for _ in range(iters):
+                calls[d]()
+            torch.digamma(marker)
+            torch.cuda.synchronize()
+            segments.append({"problem": pi, "direction": d, "iters": iters})
+        del x, w, gy
+        torch.cuda.empty_cache()
+    with open(out, "w") as f:
+        json.dump({"problems": problems, "segments": segments}, f, indent=1)
+    print(f"launched {len(segments)} stretches of {iters} calls over {len(problems)} problems; wrote {out}")
+
+
+def short(name):
+    name = " ".join(name.split())
+    name = re.sub(r"^void ", "", name)
+    m = re.match(r"([\w:]+)", name)
+    return (m.group(1) if m else name)[:60]
+
+
+def report(db, seg_file):
+    meta = json.load(open(seg_file))
+    problems, segments = meta["problems"], meta["segments"]
+    cur = sqlite3.connect(db).cursor()
+    cols = [d[0] for d in cur.execute("select * from kernels limit 1").description]
+    start = next(c for c in ("start", "start_timestamp", "start_time", "begin") if c in cols)
+    rows = cur.execute(f"select name, {start}, duration from kernels order by {start}").fetchall()
+    stretches, inside = [], None
+    for name, _, dur in rows:
+        if "erfinv" in name:
+            inside = []
+        elif "digamma" in name:
+            if inside is not None:
+                stretches.append(inside)
+            inside = None
+        elif inside is not None:
+            inside.append((short(name), dur / 1e3))
+    assert len(stretches) == len(segments), (len(stretches), len(segments))
+    print(f"# configs[1]: batch {B}, {H} x {W}, fp32.  floors: FLOPs / {MATRIX_PEAK / 1e12:.1f} TFLOP/s, operand "
+          f"bytes / {COPY_RATE / 1e12:.2f} TB/s.")
+    print("# per row: launches/step of this problem, direction, sum of the medians of one call's kernels, spread of "
+          "the calls' totals (max - min), GFLOP, MB, matrix floor, byte floor, sum / larger floor; then the kernels")
+    print("# (launches per call x median us)")
+    for seg, ks in zip(segments, stretches):
+        p = problems[seg["problem"]]
+        n = seg["iters"]
+        xs, ws, ys = p["x"], p["w"], out_shape(p)
+        numel = lambda s: s[0] * s[1] * s[2] * s[3]  # noqa: E731
+        flop = 2.0 * numel(ys) * ws[1] * ws[2] * ws[3]
+        moved = 4.0 * {"wrw": numel(xs) + numel(ys), "wrw_hip": numel(xs) + numel(ys), "bwd": numel(ys) + numel(xs),
+                       "fwd": numel(xs) + numel(ys)}[seg["direction"]] + 4.0 * numel(ws)
+        by_name = {}
+        for name, dur in ks:
+            by_name.setdefault(name, []).append(dur)
+        total, parts = 0.0, []
+        for name, ds in by_name.items():
+            ds.sort()
+            med, per_call = ds[len(ds) // 2], len(ds) / n
+            total += med * per_call
+            parts.append(f"{name} {per_call:g} x {med:.1f}")
+        # the calls' own totals: the trace is in launch order and every call launches the same sequence
+        per = len(ks) // n if n and len(ks) % n == 0 else 0
+        sums = sorted(sum(d for _, d in ks[i * per:(i + 1) * per]) for i in range(n)) if per else []
+        spread = f"{sums[-1] - sums[0]:6.1f}" if sums else "     ?"
+        f_mat, f_byte = flop / MATRIX_PEAK * 1e6, moved / COPY_RATE * 1e6
+        layers = p["layers"]
+        label = layers[0] + (f" (+{len(layers) - 1})" if len(layers) > 1 else "")
+        print(f"{p['per_step']:3d} {seg['direction']:8s} {total:8.1f} us  spread {spread}  {flop / 1e9:6.2f} GFLOP "
+              f"{moved / 1e6:7.1f} MB  floors {f_mat:6.1f} {f_byte:6.1f} us  x{total / max(f_mat, f_byte):5.2f}  "
+              f"{ws[1]}->{ws[0]} {ws[2]}x{ws[3]} s{p['stride'][0]} p{p['padding'][0]} @ {ys[2]}x{ys[3]}  {label}")
+        print("        " + "; ".join(parts))
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--out", default="segments.json", help="where the launching form writes its list of stretches")
+    ap.add_argument("--report", metavar="DB", help="read a rocprofv3 trace (trace_results.db) instead of launching")
+    ap.add_argument("--segments", default="segments.json", help="the launching form's --out, for --report")
+    args = ap.parse_args()
+    report(args.report, args.segments) if args.report else run(args.iters, args.out)
