@@ -511,3 +511,33 @@ def get_wrw() -> CLib:
                                      f"{_build.wrw_source_id()}")
                 _wrw = lib
     return _wrw
+
+
+VLOG_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_vlog.h")
+VLOG_LIB_PATH = os.path.join(HERE, "libscsfm_vlog.so")
+VLOG_ABI_VERSION = 1  # include/scsfm_vlog.h
+_vlog = None
+
+
+def get_vlog() -> CLib:
+    """The validation-log library, libscsfm_vlog.so (singleton): the validation pictures of train.py --log-output
+    (include/scsfm_vlog.h).  Built in-tree with hipcc when it is missing or stale, under the same file-lock scheme as
+    ``get()``; raises when that is impossible."""
+    global _vlog
+    if _vlog is None:
+        with _lock:
+            if _vlog is None:
+                from . import build as _build
+                if _build.vlog_is_stale():
+                    have = _build.binary_source_id(VLOG_LIB_PATH)
+                    try:
+                        _build.build_vlog()
+                    except Exception as e:
+                        raise ScsfmError(f"{VLOG_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(VLOG_LIB_PATH, VLOG_HEADER, VLOG_ABI_VERSION, "scsfm_vlog_")
+                if lib.source_id() != _build.vlog_source_id():
+                    raise ScsfmError(f"{VLOG_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.vlog_source_id()}")
+                _vlog = lib
+    return _vlog

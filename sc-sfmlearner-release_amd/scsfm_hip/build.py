@@ -1,6 +1,6 @@
 """Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so, libscsfm_stem.so,
 libscsfm_snip.so, libscsfm_prep.so, libscsfm_vis.so, libscsfm_dvis.so, libscsfm_val.so, libscsfm_enceval.so,
-libscsfm_decb.so and libscsfm_wrw.so (gfx950) in-tree with hipcc.
+libscsfm_decb.so, libscsfm_wrw.so and libscsfm_vlog.so (gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
@@ -16,7 +16,8 @@ pictures of eval_depth.py --vis_dir from csrc_dvis/*.hip; include/scsfm_val.h: t
 train.py --with-gt from csrc_val/*.hip; include/scsfm_enceval.h: the ResNet encoder's eval-mode BatchNorm / ReLU / residual /
 max-pool glue from csrc_enceval/*.hip; include/scsfm_decb.h: the depth decoder's glue with the convolutions' biases folded
 in from csrc_decb/*.hip; include/scsfm_wrw.h: the weight gradient of the depth decoder's low-channel convolutions from
-csrc_wrw/*.hip); none links against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
+csrc_wrw/*.hip; include/scsfm_vlog.h: the validation pictures of train.py --log-output from csrc_vlog/*.hip); none links
+against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
 are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
 library's id (to which recorded PMC counters are tied) unchanged.
 
@@ -69,6 +70,8 @@ DECB_CSRC = os.path.join(os.path.dirname(HERE), "csrc_decb")
 DECB_LIB = os.path.join(HERE, "libscsfm_decb.so")
 WRW_CSRC = os.path.join(os.path.dirname(HERE), "csrc_wrw")
 WRW_LIB = os.path.join(HERE, "libscsfm_wrw.so")
+VLOG_CSRC = os.path.join(os.path.dirname(HERE), "csrc_vlog")
+VLOG_LIB = os.path.join(HERE, "libscsfm_vlog.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -193,6 +196,14 @@ def wrw_deps():
     return wrw_sources() + sorted(glob.glob(os.path.join(WRW_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_wrw.h")]
 
 
+def vlog_sources():
+    return sorted(glob.glob(os.path.join(VLOG_CSRC, "*.hip")))
+
+
+def vlog_deps():
+    return vlog_sources() + sorted(glob.glob(os.path.join(VLOG_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_vlog.h")]
+
+
 def _hash(files, extra=()):
     h = hashlib.sha256()
     for path in files:
@@ -284,6 +295,11 @@ def wrw_source_id():
     return _hash(wrw_deps())
 
 
+def vlog_source_id():
+    """source_id() of libscsfm_vlog.so: its own sources (csrc_vlog/, include/scsfm_vlog.h) and the compiler flags."""
+    return _hash(vlog_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -353,6 +369,10 @@ def decb_is_stale():
 
 def wrw_is_stale():
     return binary_source_id(WRW_LIB) != wrw_source_id()
+
+
+def vlog_is_stale():
+    return binary_source_id(VLOG_LIB) != vlog_source_id()
 
 
 @contextlib.contextmanager
@@ -443,6 +463,11 @@ def build_wrw(force=False, verbose=True):
     return _build(WRW_LIB, wrw_source_id(), wrw_sources(), ("-I", INCLUDE), force, verbose)
 
 
+def build_vlog(force=False, verbose=True):
+    """build() for libscsfm_vlog.so: every .hip file under csrc_vlog/, against include/scsfm_vlog.h."""
+    return _build(VLOG_LIB, vlog_source_id(), vlog_sources(), ("-I", INCLUDE), force, verbose)
+
+
 def _build(lib, want, srcs, extra, force, verbose):
     if not force and binary_source_id(lib) == want:
         return lib
@@ -486,6 +511,7 @@ if __name__ == "__main__":
     build_enceval(force="--force" in sys.argv)
     build_decb(force="--force" in sys.argv)
     build_wrw(force="--force" in sys.argv)
+    build_vlog(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
     print(EVAL_LIB)
@@ -500,3 +526,4 @@ if __name__ == "__main__":
     print(ENCEVAL_LIB)
     print(DECB_LIB)
     print(WRW_LIB)
+    print(VLOG_LIB)

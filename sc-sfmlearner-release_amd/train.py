@@ -15,7 +15,8 @@ Differences from the reference, all forced by the platform or by the scale-out d
     `--pretrained-disp/--pretrained-pose`.
   * DATA may be `synthetic:N:HxW` (extension): N in-memory random sequences, for smoke / throughput runs.
   * tensorboardX / blessings / progressbar2 / path are not installed: scalars go to the two TSV logs
-    (same files and columns as the reference) and to stdout.
+    (same files and columns as the reference) and to stdout; with `--log-output` the validation pictures are
+    made on the GPU (scsfm_hip/validation_log.py) and written as PNG files under `<save_path>/valid/0..2`.
   * `torch.autograd.set_detect_anomaly(True)` (train.py:67) is not enabled: the kernels are NaN-free.
 """
 import argparse
@@ -40,6 +41,7 @@ except ImportError:
 from scsfm_hip import config as hip_config
 from scsfm_hip import dist as hip_dist
 from scsfm_hip import validation as hip_validation
+from scsfm_hip import validation_log as hip_validation_log
 from utils import save_checkpoint
 
 parser = argparse.ArgumentParser(description='Structure from Motion Learner training on KITTI and CityScapes Dataset',
@@ -106,20 +108,37 @@ device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cp
 class _ScalarLog(object):
     """Stand-in for tensorboardX.SummaryWriter (train.py:85-89 of the reference; the package is absent here): keeps
     the call sites and drops the data -- saying so once on stdout.  The two TSV logs (progress_log_*.csv) carry
-    the same scalars."""
+    the same scalars; the pictures of --log-output go to scsfm_hip.validation_log.PictureLog instead."""
     _announced = False
 
     def _announce(self):
         if not _ScalarLog._announced:
             _ScalarLog._announced = True
-            print("=> tensorboardX is not installed: TensorBoard scalars / images are not written "
-                  "(losses are in progress_log_full.csv and progress_log_summary.csv)")
+            print("=> tensorboardX is not installed: TensorBoard scalars are not written "
+                  "(losses are in progress_log_full.csv and progress_log_summary.csv; "
+                  "--log-output writes its pictures as PNG files under <save_path>/valid)")
 
     def add_scalar(self, *a, **k):
         self._announce()
 
     def add_image(self, *a, **k):
         self._announce()
+
+
+def make_output_writers(args):
+    """The three writers of the reference's --log-output (train.py:88-90: SummaryWriter(save_path/'valid'/str(i))), as
+    PictureLogs that write PNG files; none without the flag."""
+    if not args.log_output:
+        return []
+    return [hip_validation_log.PictureLog(os.path.join(args.save_path, 'valid', str(i))) for i in range(3)]
+
+
+def log_disparity(writer, disp, depth, epoch):
+    """The two pictures both validation loops write for one image (train.py:332-337, :403-408): the disparity in magma
+    over its own maximum, the depth in rainbow over 10.  ``disp`` and ``depth``: [1, H, W] on the device."""
+    writer.add_image('val Dispnet Output Normalized',
+                     hip_validation_log.map_pictures(disp, 'magma', None, floats=False)[1][0], epoch)
+    writer.add_image('val Depth Output', hip_validation_log.map_pictures(depth, 'rainbow', 10, floats=False)[1][0], epoch)
 
 
 def build_datasets(args):
@@ -198,7 +217,7 @@ def main():
               "per-layer solver search: SCSFM_CUDNN_BENCHMARK=1 turns it on)".format(torch.backends.cudnn.benchmark))
 
     training_writer = _ScalarLog()
-    output_writers = [_ScalarLog() for _ in range(3)] if args.log_output else []
+    output_writers = make_output_writers(args) if is_main else []  # (rank 0 validates)
 
     if is_main:
         print("=> fetching scenes in '{}'".format(args.data))
@@ -270,10 +289,7 @@ def main():
             logger.reset_valid_bar()
             d_net = disp_net.module if world > 1 else disp_net
             p_net = pose_net.module if world > 1 else pose_net
-            if args.with_gt:
-                errors, error_names = validate_with_gt(args, val_loader, d_net, epoch, logger, output_writers)
-            else:
-                errors, error_names = validate_without_gt(args, val_loader, d_net, p_net, epoch, logger, output_writers)
+            errors, error_names = validate(args, val_loader, d_net, p_net, epoch, logger, output_writers)
             logger.valid_writer.write(' * Avg {}'.format(', '.join('{} : {:.3f}'.format(n, e) for n, e in zip(error_names, errors))))
             for error, name in zip(errors, error_names):
                 training_writer.add_scalar(name, error, epoch)
@@ -406,6 +422,14 @@ def train(args, train_loader, disp_net, pose_net, optimizer, epoch_size, logger,
     return losses.avg[0]
 
 
+def validate(args, val_loader, disp_net, pose_net, epoch, logger, output_writers=[]):
+    """One validation pass of main() (train.py:206-209 of the reference): against ground truth with --with-gt, the
+    losses otherwise; the writers of --log-output go to whichever runs."""
+    if args.with_gt:
+        return validate_with_gt(args, val_loader, disp_net, epoch, logger, output_writers)
+    return validate_without_gt(args, val_loader, disp_net, pose_net, epoch, logger, output_writers)
+
+
 @torch.no_grad()
 def validate_without_gt(args, val_loader, disp_net, pose_net, epoch, logger, output_writers=[]):
     """Photometric / smoothness / geometry losses on the validation split, auto-mask off
@@ -423,6 +447,10 @@ def validate_without_gt(args, val_loader, disp_net, pose_net, epoch, logger, out
         intrinsics = intrinsics.to(device).float()
         tgt_depth = [1 / disp_net(tgt_img)]
         ref_depths = [[1 / disp_net(ref_img)] for ref_img in ref_imgs]
+        if i < len(output_writers):  # (train.py:328-337)
+            if epoch == 0:
+                output_writers[i].add_image('val Input', hip_validation_log.input_pictures(tgt_img[:1], floats=False)[1][0], 0)
+            log_disparity(output_writers[i], 1 / tgt_depth[0][0], tgt_depth[0][0], epoch)
         poses, poses_inv = compute_pose_with_inv(pose_net, tgt_img, ref_imgs)
         loss_1, loss_3 = compute_photo_and_geometry_loss(tgt_img, ref_imgs, intrinsics, tgt_depth, ref_depths, poses, poses_inv,
                                                          args.num_scales, args.with_ssim, args.with_mask, False, args.padding_mode)
@@ -454,6 +482,15 @@ def validate_with_gt(args, val_loader, disp_net, epoch, logger, output_writers=[
         if depth.nelement() == 0:
             continue
         output_disp = disp_net(tgt_img)
+        if i < len(output_writers):  # (train.py:390-408; the ground truth is shown without the in-place write of :397)
+            if epoch == 0:
+                output_writers[i].add_image('val Input', hip_validation_log.input_pictures(tgt_img[:1], floats=False)[1][0], 0)
+                output_writers[i].add_image('val target Depth',
+                                            hip_validation_log.map_pictures(depth[:1], 'rainbow', 10, floats=False)[1][0], epoch)
+                output_writers[i].add_image('val target Disparity Normalized',
+                                            hip_validation_log.map_pictures(hip_validation_log.target_disparity(depth[:1]),
+                                                                            'magma', None, floats=False)[1][0], epoch)
+            log_disparity(output_writers[i], output_disp[0], 1 / output_disp[:1, 0], epoch)
         # 1 / disp, the nearest resize to the ground truth's size and compute_errors' per-image loop: one library call
         errors.update(hip_validation.batch_mean(hip_validation.depth_errors(depth, output_disp, args.dataset, is_disp=True)))
         batch_time.update(time.time() - end)
