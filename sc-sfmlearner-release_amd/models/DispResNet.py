@@ -129,13 +129,17 @@ class DepthDecoder(nn.Module):
         that glue's backward sums: ATen's broadcast add after each convolution and its grad_output.sum((0, 2, 3)) no
         longer run as passes of their own.  The low-channel convolutions that scsfm_hip.conv_wrw routes take their weight
         gradient from libscsfm_wrw.so (SCSFM_DECODER_WRW=0: MIOpen's, as every other layer).  Conv (0, 1) without a head at scale 0 has no glue behind it and keeps its
-        module call."""
-        from scsfm_hip import conv_wrw as CW, decoder as D, decoder_bias as DB
+        module call.  At level 0 the padded tensor feeds the head alone: elu_pad, the head's convolution and disp_head
+        are one autograd node there (scsfm_hip.decoder_dgrad.head_tail: the same three launches forward, one streaming
+        kernel from libscsfm_dgrad.so backward; SCSFM_DECODER_DGRAD=0: the three nodes, as at the other levels)."""
+        from scsfm_hip import conv_wrw as CW, decoder as D, decoder_bias as DB, decoder_dgrad as DG
 
         def conv(k, x):
             m = self._conv(k)
             if CW.applies(x, m):  # (the weight gradient from libscsfm_wrw.so)
                 return CW.conv3x3_valid(x, m.weight), m.bias
+            if CW.applies_without_wrw(x, m):  # (SCSFM_DECODER_WRW=0: the input gradient alone from libscsfm_dgrad.so)
+                return CW.conv3x3_valid(x, m.weight, wrw=False), m.bias
             return F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups), m.bias
 
         outputs = []
@@ -147,6 +151,10 @@ class DepthDecoder(nn.Module):
                 self._conv(self._up[(i, 1)])(x)
                 break
             b, bias = conv(self._up[(i, 1)], x)
+            if i == 0 and DG.applies(b, bias, self._conv(self._head[0])):
+                head = self._conv(self._head[0])
+                outputs.append(DG.head_tail(b, bias, head.weight, head.bias, self.alpha, self.beta))
+                break
             x = DB.elu_pad(b, bias)
             if i in self._head:
                 h, bias = conv(self._head[i], x)

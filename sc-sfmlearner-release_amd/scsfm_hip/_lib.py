@@ -541,3 +541,33 @@ def get_vlog() -> CLib:
                                      f"{_build.vlog_source_id()}")
                 _vlog = lib
     return _vlog
+
+
+DGRAD_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "scsfm_dgrad.h")
+DGRAD_LIB_PATH = os.path.join(HERE, "libscsfm_dgrad.so")
+DGRAD_ABI_VERSION = 1  # include/scsfm_dgrad.h
+_dgrad = None
+
+
+def get_dgrad() -> CLib:
+    """The tail-backward library, libscsfm_dgrad.so (singleton): the backward of the depth decoder's full-resolution
+    tail (ELU / pad / disparity head) as one streaming kernel (include/scsfm_dgrad.h).  Built in-tree with hipcc when it
+    is missing or stale, under the same file-lock scheme as ``get()``; raises when that is impossible."""
+    global _dgrad
+    if _dgrad is None:
+        with _lock:
+            if _dgrad is None:
+                from . import build as _build
+                if _build.dgrad_is_stale():
+                    have = _build.binary_source_id(DGRAD_LIB_PATH)
+                    try:
+                        _build.build_dgrad()
+                    except Exception as e:
+                        raise ScsfmError(f"{DGRAD_LIB_PATH} is stale or missing ({have}) and cannot be built here: {e}") \
+                            from e
+                lib = CLib(DGRAD_LIB_PATH, DGRAD_HEADER, DGRAD_ABI_VERSION, "scsfm_dgrad_")
+                if lib.source_id() != _build.dgrad_source_id():
+                    raise ScsfmError(f"{DGRAD_LIB_PATH}: its source id {lib.source_id()} is not the tree's "
+                                     f"{_build.dgrad_source_id()}")
+                _dgrad = lib
+    return _dgrad

@@ -1,6 +1,6 @@
 """Build libscsfm_hip.so, libscsfm_nets.so, libscsfm_eval.so, libscsfm_odom.so, libscsfm_enc.so, libscsfm_stem.so,
 libscsfm_snip.so, libscsfm_prep.so, libscsfm_vis.so, libscsfm_dvis.so, libscsfm_val.so, libscsfm_enceval.so,
-libscsfm_decb.so, libscsfm_wrw.so and libscsfm_vlog.so (gfx950) in-tree with hipcc.
+libscsfm_decb.so, libscsfm_wrw.so, libscsfm_vlog.so and libscsfm_dgrad.so (gfx950) in-tree with hipcc.
 
     python -m scsfm_hip.build        (from sc-sfmlearner-release_amd/)
 
@@ -16,7 +16,8 @@ pictures of eval_depth.py --vis_dir from csrc_dvis/*.hip; include/scsfm_val.h: t
 train.py --with-gt from csrc_val/*.hip; include/scsfm_enceval.h: the ResNet encoder's eval-mode BatchNorm / ReLU / residual /
 max-pool glue from csrc_enceval/*.hip; include/scsfm_decb.h: the depth decoder's glue with the convolutions' biases folded
 in from csrc_decb/*.hip; include/scsfm_wrw.h: the weight gradient of the depth decoder's low-channel convolutions from
-csrc_wrw/*.hip; include/scsfm_vlog.h: the validation pictures of train.py --log-output from csrc_vlog/*.hip); none links
+csrc_wrw/*.hip; include/scsfm_vlog.h: the validation pictures of train.py --log-output from csrc_vlog/*.hip;
+include/scsfm_dgrad.h: the backward of the depth decoder's full-resolution tail from csrc_dgrad/*.hip); none links
 against torch.  They are written next to this file so that they travel with the source tree to the GPU box.  They
 are separate targets with separate source ids, so that an edit of the nets' or the evaluation's kernels leaves the loss
 library's id (to which recorded PMC counters are tied) unchanged.
@@ -72,6 +73,8 @@ WRW_CSRC = os.path.join(os.path.dirname(HERE), "csrc_wrw")
 WRW_LIB = os.path.join(HERE, "libscsfm_wrw.so")
 VLOG_CSRC = os.path.join(os.path.dirname(HERE), "csrc_vlog")
 VLOG_LIB = os.path.join(HERE, "libscsfm_vlog.so")
+DGRAD_CSRC = os.path.join(os.path.dirname(HERE), "csrc_dgrad")
+DGRAD_LIB = os.path.join(HERE, "libscsfm_dgrad.so")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -204,6 +207,15 @@ def vlog_deps():
     return vlog_sources() + sorted(glob.glob(os.path.join(VLOG_CSRC, "*.h"))) + [os.path.join(INCLUDE, "scsfm_vlog.h")]
 
 
+def dgrad_sources():
+    return sorted(glob.glob(os.path.join(DGRAD_CSRC, "*.hip")))
+
+
+def dgrad_deps():
+    return dgrad_sources() + sorted(glob.glob(os.path.join(DGRAD_CSRC, "*.h"))) + \
+        [os.path.join(INCLUDE, "scsfm_dgrad.h")]
+
+
 def _hash(files, extra=()):
     h = hashlib.sha256()
     for path in files:
@@ -300,6 +312,11 @@ def vlog_source_id():
     return _hash(vlog_deps())
 
 
+def dgrad_source_id():
+    """source_id() of libscsfm_dgrad.so: its own sources (csrc_dgrad/, include/scsfm_dgrad.h) and the compiler flags."""
+    return _hash(dgrad_deps())
+
+
 def binary_source_id(path=LIB):
     """The source id compiled into the shared object at ``path``, read from the file (no dlopen: a stale or foreign
     binary may lack symbols the loader insists on).  None if there is no such file or it carries no id."""
@@ -373,6 +390,10 @@ def wrw_is_stale():
 
 def vlog_is_stale():
     return binary_source_id(VLOG_LIB) != vlog_source_id()
+
+
+def dgrad_is_stale():
+    return binary_source_id(DGRAD_LIB) != dgrad_source_id()
 
 
 @contextlib.contextmanager
@@ -468,6 +489,11 @@ def build_vlog(force=False, verbose=True):
     return _build(VLOG_LIB, vlog_source_id(), vlog_sources(), ("-I", INCLUDE), force, verbose)
 
 
+def build_dgrad(force=False, verbose=True):
+    """build() for libscsfm_dgrad.so: every .hip file under csrc_dgrad/, against include/scsfm_dgrad.h."""
+    return _build(DGRAD_LIB, dgrad_source_id(), dgrad_sources(), ("-I", INCLUDE), force, verbose)
+
+
 def _build(lib, want, srcs, extra, force, verbose):
     if not force and binary_source_id(lib) == want:
         return lib
@@ -512,6 +538,7 @@ if __name__ == "__main__":
     build_decb(force="--force" in sys.argv)
     build_wrw(force="--force" in sys.argv)
     build_vlog(force="--force" in sys.argv)
+    build_dgrad(force="--force" in sys.argv)
     print(LIB)
     print(NETS_LIB)
     print(EVAL_LIB)
@@ -527,3 +554,4 @@ if __name__ == "__main__":
     print(DECB_LIB)
     print(WRW_LIB)
     print(VLOG_LIB)
+    print(DGRAD_LIB)

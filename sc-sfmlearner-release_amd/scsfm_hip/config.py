@@ -131,3 +131,23 @@ def decoder_wrw():
 def set_decoder_wrw(on):
     global _decoder_wrw
     _decoder_wrw = None if on is None else bool(on)
+
+
+_decoder_dgrad = None
+
+
+def decoder_dgrad():
+    """Does the depth decoder's full-resolution tail (ELU / pad / disparity head at level 0) take its backward from
+    libscsfm_dgrad.so (scsfm_hip.decoder_dgrad.head_tail) instead of the head's sigmoid backward, MIOpen's data gradient
+    and the pad / ELU backward as launches of their own?  Default on; SCSFM_DECODER_DGRAD=0 (read once) or
+    set_decoder_dgrad(False) restore those calls exactly."""
+    global _decoder_dgrad
+    if _decoder_dgrad is None:
+        import os
+        _decoder_dgrad = os.environ.get("SCSFM_DECODER_DGRAD", "1") != "0"
+    return _decoder_dgrad
+
+
+def set_decoder_dgrad(on):
+    global _decoder_dgrad
+    _decoder_dgrad = None if on is None else bool(on)

@@ -8,13 +8,21 @@ they take, and what the shape allows.
 The first form collects the problems (a dispatch mode records every aten.convolution of one training-mode forward of
 each net, with the module that owns the weight) and launches, per problem, aten.convolution_backward with the output mask
 [False, True, False] (weight only), with [True, False, False] (input only) and the forward, `--iters` times each after 3
-warm-up calls; for the problems scsfm_hip.conv_wrw covers it also launches libscsfm_wrw.so's weight gradient.  Each
+warm-up calls; for the problems scsfm_hip.conv_wrw covers it also launches libscsfm_wrw.so's weight gradient (`wrw_hip`)
+and libscsfm_dgrad.so's data gradient (`bwd_hip`).  Each
 timed stretch lies between two marker kernels (erfinv in front, digamma behind: nothing else here launches them), so
 the report can tell which kernels belong to it.  The second form reads the trace and prints one row per problem and
 direction: launches per step of the training loop (3 DispResNet passes, 4 PoseResNet passes), the kernels of one call
 (convolution, transposes, casts, zero-fill) with their launches per call and median durations, their sum, the FLOPs
 and the bytes the operands hold, and the two floors: FLOPs / 157 TFLOP/s (the fp32 matrix peak) and bytes / 6.29 TB/s
-(the measured copy rate)."""
+(the measured copy rate).
+
+Behind the convolution problems comes the backward of the decoder's full-resolution tail (level 0: ELU, pad, disparity
+head), as the launches it used to be (direction `tail`: the head's sigmoid backward with its bias sum, MIOpen's data
+gradient of the 16 -> 1 convolution, the pad / ELU backward with its bias sum) and as libscsfm_dgrad.so's one pass
+(`tail_hip`); its bytes are what the one pass has to move (the padded tensor, the gradient it stores, three planes).
+`--tail-only` launches these two stretches alone, `--dgrad-only` these and the data gradients (`bwd`, `bwd_hip`) of the
+problems libscsfm_dgrad.so covers."""
 import argparse
 import json
 import os
@@ -30,7 +38,8 @@ COPY_RATE = 6.29e12    # bytes/s, the measured copy rate of one MI355X (DESIGN.m
 MATRIX_PEAK = 157.3e12  # fp32 FLOP/s of v_mfma_f32_*_f32
 B, H, W = 12, 256, 832
 PASSES = {"disp": 3, "pose": 4}  # per training step with two reference frames
-DIRECTIONS = ("wrw", "bwd", "fwd", "wrw_hip")
+DIRECTIONS = ("wrw", "bwd", "fwd", "wrw_hip", "bwd_hip", "tail", "tail_hip")
+TAIL_C = 16
 
 
 def collect():
@@ -81,16 +90,61 @@ def out_shape(p):
     return (b, co, ho, wo)
 
 
-def run(iters, out):
+def tail_calls(torch):
+    """-> the tail's problem entry and its two calls"""
+    from scsfm_hip import _lib, decoder_dgrad as DG
+    from scsfm_hip.decoder_bias import _bias_sum_buffers
+    q = torch.rand(B, TAIL_C, H + 2, W + 2, device="cuda") * 3 - 1
+    y = torch.rand(B, 1, H, W, device="cuda")
+    g_out = torch.randn(B, 1, H, W, device="cuda")
+    w = torch.randn(1, TAIL_C, 3, 3, device="cuda")
+    decb = _lib.get_decb()
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def parts():
+        g = torch.empty_like(y)
+        ws, g_bias = _bias_sum_buffers(decb, y, True, B, 1, 1, H * W)
+        decb.call("scsfm_decb_disp_head_bwd_f32", B, 1, H, W, 10.0, g_out.data_ptr(), y.data_ptr(), g.data_ptr(),
+                  ws.data_ptr(), g_bias.data_ptr(), stream)
+        gq = torch.ops.aten.convolution_backward(g, q, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+                                                 [True, False, False])[0]
+        g_b = torch.empty(B, TAIL_C, H, W, device="cuda")
+        ws, g_bias = _bias_sum_buffers(decb, y, True, B, TAIL_C, H, W)
+        decb.call("scsfm_decb_bias_elu_pad_bwd_f32", B, TAIL_C, H, W, gq.data_ptr(), q.data_ptr(), g_b.data_ptr(),
+                  ws.data_ptr(), g_bias.data_ptr(), stream)
+        return g_b
+
+    problem = {"x": tuple(q.shape), "w": tuple(w.shape), "stride": (1, 1), "padding": (0, 0), "dilation": (1, 1),
+               "groups": 1, "layers": ["disp.decoder: the tail of level 0, backward"], "per_step": PASSES["disp"]}
+    return problem, {"tail": parts, "tail_hip": lambda: DG.tail_bwd(q, y, g_out, w, 10.0)}
+
+
+def run(iters, out, tail_only=False, dgrad_only=False):
     import torch
 
     from bench import MIOPEN_SOLVERS_NEVER_CHOSEN
     for k in MIOPEN_SOLVERS_NEVER_CHOSEN:  # (the search space of bench.py's runs)
         os.environ.setdefault(k, "0")
     from scsfm_hip import conv_wrw as CW
-    problems = collect()
+    problems = [] if tail_only else collect()
+    covered = lambda p: (p["w"][2:] == (3, 3) and p["stride"] == (1, 1) and p["padding"] == (0, 0)  # noqa: E731
+                         and p["groups"] == 1 and CW.dgrad_covers(p["w"][1], p["w"][0]))
+    if dgrad_only:
+        problems = [p for p in problems if covered(p)]
     marker = torch.rand(64, device="cuda") * 0.5
     segments = []
+
+    def stretch(pi, d, call):
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize()
+        torch.erfinv(marker)
+        for _ in range(iters):
+            call()
+        torch.digamma(marker)
+        torch.cuda.synchronize()
+        segments.append({"problem": pi, "direction": d, "iters": iters})
+
     for pi, p in enumerate(problems):
         x = torch.randn(*p["x"], device="cuda")
         w = torch.randn(*p["w"], device="cuda")
@@ -105,20 +159,19 @@ def run(iters, out):
         plain3x3 = p["w"][2:] == (3, 3) and p["stride"] == (1, 1) and p["padding"] == (0, 0) and p["groups"] == 1
         if plain3x3 and CW.covers(p["w"][1], p["w"][0]):
             calls["wrw_hip"] = lambda: CW.weight_grad(x, gy)
+        if covered(p):
+            calls["bwd_hip"] = lambda: CW.data_grad(gy, w)
+        if dgrad_only:
+            calls = {d: c for d, c in calls.items() if d in ("bwd", "bwd_hip")}
         for d in DIRECTIONS:
-            if d not in calls:
-                continue
-            for _ in range(3):
-                calls[d]()
-            torch.cuda.synchronize()
-            torch.erfinv(marker)
-            for _ in range(iters):
-                calls[d]()
-            torch.digamma(marker)
-            torch.cuda.synchronize()
-            segments.append({"problem": pi, "direction": d, "iters": iters})
+            if d in calls:
+                stretch(pi, d, calls[d])
         del x, w, gy
         torch.cuda.empty_cache()
+    tail, calls = tail_calls(torch)
+    problems.append(tail)
+    for d, call in calls.items():
+        stretch(len(problems) - 1, d, call)
     with open(out, "w") as f:
         json.dump({"problems": problems, "segments": segments}, f, indent=1)
     print(f"launched {len(segments)} stretches of {iters} calls over {len(problems)} problems; wrote {out}")
@@ -161,7 +214,9 @@ def report(db, seg_file):
         numel = lambda s: s[0] * s[1] * s[2] * s[3]  # noqa: E731
         flop = 2.0 * numel(ys) * ws[1] * ws[2] * ws[3]
         moved = 4.0 * {"wrw": numel(xs) + numel(ys), "wrw_hip": numel(xs) + numel(ys), "bwd": numel(ys) + numel(xs),
-                       "fwd": numel(xs) + numel(ys)}[seg["direction"]] + 4.0 * numel(ws)
+                       "bwd_hip": numel(ys) + numel(xs),
+                       "fwd": numel(xs) + numel(ys), "tail": numel(xs) + (ws[1] + 3) * numel(ys),
+                       "tail_hip": numel(xs) + (ws[1] + 3) * numel(ys)}[seg["direction"]] + 4.0 * numel(ws)
         by_name = {}
         for name, dur in ks:
             by_name.setdefault(name, []).append(dur)
@@ -190,5 +245,8 @@ if __name__ == "__main__":
     ap.add_argument("--out", default="segments.json", help="where the launching form writes its list of stretches")
     ap.add_argument("--report", metavar="DB", help="read a rocprofv3 trace (trace_results.db) instead of launching")
     ap.add_argument("--segments", default="segments.json", help="the launching form's --out, for --report")
+    ap.add_argument("--tail-only", action="store_true", help="launch the two stretches of the decoder's tail alone")
+    ap.add_argument("--dgrad-only", action="store_true",
+                    help="launch the tail and the data gradients of the problems libscsfm_dgrad.so covers alone")
     args = ap.parse_args()
-    report(args.report, args.segments) if args.report else run(args.iters, args.out)
+    report(args.report, args.segments) if args.report else run(args.iters, args.out, args.tail_only, args.dgrad_only)
