@@ -1,0 +1,63 @@
+"""The one table of the HIP libraries.  scsfm_hip/build.py compiles its rows, scsfm_hip/_lib.py loads them,
+__graft_entry__.build() reports them and tests/hostsim/library.py compiles them for the host simulator.
+
+A row holds what cannot be derived: the short name ("" for the loss library), the ABI version its header states, the
+tag build() reports it under and one line on what it computes.  The source directory, the header, the shared object and
+the symbol prefix follow from the short name.  Imports nothing but os, so that scsfm_hip._lib can read it on import.
+"""
+from __future__ import annotations
+
+import os
+from typing import NamedTuple
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
+
+
+class Library(NamedTuple):
+    name: str  # "" for the loss library
+    abi: int   # what <prefix>abi_version() returns, as include/<header> states it
+    tag: str   # __graft_entry__.build() prints "[<tag>] <path>: <n> entry points resolved"
+    what: str
+
+    @property
+    def csrc(self):
+        return os.path.join(os.path.dirname(HERE), "csrc_" + self.name if self.name else "csrc")
+
+    @property
+    def header(self):
+        return os.path.join(INCLUDE, f"scsfm_{self.name or 'hip'}.h")
+
+    @property
+    def lib(self):
+        return os.path.join(HERE, f"libscsfm_{self.name or 'hip'}.so")
+
+    @property
+    def prefix(self):
+        return f"scsfm_{self.name}_" if self.name else "scsfm_"
+
+
+TABLE = (
+    Library("", 9, "build", "the loss path"),
+    Library("nets", 1, "build", "the depth decoder's fused glue"),
+    Library("eval", 1, "build", "depth evaluation with median scaling"),
+    Library("odom", 1, "build", "the pose chain of test_vo.py and KITTI odometry evaluation"),
+    Library("enc", 1, "build", "the ResNet encoder's fused BatchNorm / ReLU / residual / max-pool glue"),
+    Library("stem", 1, "build", "the ResNet stem's BatchNorm / ReLU fused with its max-pool"),
+    Library("snip", 1, "build", "the 5-frame snippet pose evaluation of test_pose.py"),
+    Library("prep", 1, "build:prep", "the resize and the Velodyne depth maps of data/prepare_train_data.py"),
+    Library("vis", 1, "build:vis", "the input normalisation, the per-image maximum and the colour-mapped pictures of "
+                                   "run_inference.py"),
+    Library("dvis", 1, "build:dvis", "the scaled prediction, the colour range and the magma pictures of eval_depth.py "
+                                     "--vis_dir"),
+    Library("val", 1, "val:build", "the ground-truth validation metrics of train.py --with-gt"),
+    Library("enceval", 1, "enceval:build", "the ResNet encoder's eval-mode BatchNorm / ReLU / residual / max-pool glue"),
+    Library("decb", 1, "decb:build", "the depth decoder's glue with the convolutions' biases folded in"),
+    Library("wrw", 1, "wrw:build", "the weight gradient of the depth decoder's low-channel 3x3 convolutions"),
+    Library("vlog", 1, "vlog:build", "the validation pictures of train.py --log-output"),
+    Library("dgrad", 1, "dgrad:build", "the backward of the depth decoder's full-resolution tail"),
+)
+BY_NAME = {row.name: row for row in TABLE}
+# one line per library, for the docstrings of build.py and _lib.py
+SUMMARY = "\n".join(f"    {os.path.basename(row.lib):22s} {os.path.basename(row.csrc) + '/':14s} "
+                    f"include/{os.path.basename(row.header):16s} {row.what}" for row in TABLE)

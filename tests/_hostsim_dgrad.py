@@ -8,15 +8,14 @@ from __future__ import annotations
 
 import ctypes
 import functools
-import glob
 import os
-import subprocess
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 import _hostsim_decb as HB
+from hostsim import library
 from scsfm_hip._lib import DGRAD_ABI_VERSION, DGRAD_HEADER, CLib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -30,18 +29,7 @@ GUARD_MAX = 1 << 16
 
 
 def build(force=False, src=SRC, lib=LIB):
-    srcs = sorted(glob.glob(os.path.join(src, "*.hip")))
-    deps = srcs + glob.glob(os.path.join(src, "*.h")) + [os.path.join(HOSTSIM, "hip", "hip_runtime.h"), SHIM,
-                                                          DGRAD_HEADER, os.path.abspath(__file__)]
-    if not force and os.path.exists(lib) and all(os.path.getmtime(d) <= os.path.getmtime(lib) for d in deps):
-        return lib
-    os.makedirs(os.path.dirname(lib), exist_ok=True)
-    tmp = f"{lib}.{os.getpid()}.tmp"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-x", "c++", "-I", HOSTSIM,
-                    "-I", os.path.dirname(DGRAD_HEADER), "-include", SHIM, "-Wall", "-Wno-unused-function",
-                    "-Wno-unknown-pragmas", "-o", tmp, *srcs], check=True)
-    os.replace(tmp, lib)
-    return lib
+    return library.build("dgrad", force, src, lib, shim=SHIM, dep=os.path.abspath(__file__))
 
 
 @functools.lru_cache(maxsize=1)

@@ -9,13 +9,12 @@ from __future__ import annotations
 
 import ctypes
 import functools
-import glob
 import os
-import subprocess
 
 import numpy as np
 import torch
 
+from hostsim import library
 from scsfm_hip._lib import NETS_ABI_VERSION, NETS_HEADER, CLib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -28,18 +27,7 @@ LIB = os.path.join(OUT, "libscsfm_nets_hostsim.so")
 
 
 def build(force=False, src=SRC, lib=LIB):
-    srcs = sorted(glob.glob(os.path.join(src, "*.hip")))
-    deps = srcs + glob.glob(os.path.join(src, "*.h")) + [os.path.join(HOSTSIM, "hip", "hip_runtime.h"), SHIM,
-                                                          NETS_HEADER, os.path.abspath(__file__)]
-    if not force and os.path.exists(lib) and all(os.path.getmtime(d) <= os.path.getmtime(lib) for d in deps):
-        return lib
-    os.makedirs(os.path.dirname(lib), exist_ok=True)
-    tmp = f"{lib}.{os.getpid()}.tmp"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-x", "c++", "-I", HOSTSIM,
-                    "-I", os.path.dirname(NETS_HEADER), "-include", SHIM, "-Wall", "-Wno-unused-function",
-                    "-Wno-unknown-pragmas", "-o", tmp, *srcs], check=True)
-    os.replace(tmp, lib)
-    return lib
+    return library.build("nets", force, src, lib, shim=SHIM, dep=os.path.abspath(__file__))
 
 
 @functools.lru_cache(maxsize=1)

@@ -5,12 +5,11 @@ from __future__ import annotations
 
 import ctypes
 import functools
-import glob
 import os
-import subprocess
 
 import numpy as np
 
+from hostsim import library
 from scsfm_hip import prepare
 from scsfm_hip._lib import PREP_ABI_VERSION, PREP_HEADER, CLib
 
@@ -23,18 +22,7 @@ LIB = os.path.join(OUT, "libscsfm_prep_hostsim.so")
 
 
 def build(force=False):
-    srcs = sorted(glob.glob(os.path.join(SRC, "*.hip")))
-    deps = srcs + glob.glob(os.path.join(SRC, "*.h")) + [os.path.join(HOSTSIM, "hip", "hip_runtime.h"), PREP_HEADER,
-                                                          os.path.abspath(__file__)]
-    if not force and os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    os.makedirs(OUT, exist_ok=True)
-    tmp = f"{LIB}.{os.getpid()}.tmp"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-x", "c++", "-I", HOSTSIM,
-                    "-I", os.path.dirname(PREP_HEADER), "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                    "-o", tmp, *srcs], check=True)
-    os.replace(tmp, LIB)
-    return LIB
+    return library.build("prep", force, dep=os.path.abspath(__file__))
 
 
 @functools.lru_cache(maxsize=1)

@@ -5,13 +5,12 @@ from __future__ import annotations
 
 import ctypes
 import functools
-import glob
 import os
-import subprocess
 
 import numpy as np
 
 import validation_errors_oracle as O
+from hostsim import library
 from scsfm_hip._lib import VAL_ABI_VERSION, VAL_HEADER, CLib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -26,18 +25,7 @@ SENTINEL = {"metrics": -12345.5, "medians": -54321.5, "count": -77}
 
 
 def build(force=False):
-    srcs = sorted(glob.glob(os.path.join(SRC, "*.hip")))
-    deps = srcs + glob.glob(os.path.join(SRC, "*.h")) + [os.path.join(HOSTSIM, "hip", "hip_runtime.h"), VAL_HEADER,
-                                                          os.path.abspath(__file__)]
-    if not force and os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    os.makedirs(OUT, exist_ok=True)
-    tmp = f"{LIB}.{os.getpid()}.tmp"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-x", "c++", "-I", HOSTSIM,
-                    "-I", os.path.dirname(VAL_HEADER), "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                    "-o", tmp, *srcs], check=True)
-    os.replace(tmp, LIB)
-    return LIB
+    return library.build("val", force, dep=os.path.abspath(__file__))
 
 
 @functools.lru_cache(maxsize=1)
