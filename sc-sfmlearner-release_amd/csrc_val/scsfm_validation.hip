@@ -313,7 +313,7 @@ inline bool layout(int B, int H, int W, Layout* L) {
 
 extern "C" {
 
-int scsfm_val_abi_version(void) { return 1; }
+int scsfm_val_abi_version(void) { return 2; }
 
 #ifndef SCSFM_SOURCE_ID
 #define SCSFM_SOURCE_ID "unknown"

@@ -50,7 +50,8 @@ TABLE = (
                                    "run_inference.py"),
     Library("dvis", 1, "build:dvis", "the scaled prediction, the colour range and the magma pictures of eval_depth.py "
                                      "--vis_dir"),
-    Library("val", 1, "val:build", "the ground-truth validation metrics of train.py --with-gt"),
+    Library("val", 2, "val:build", "the validation pass of train.py: the ground-truth metrics of --with-gt and the "
+                                   "per-batch table of --shard-validation"),
     Library("enceval", 1, "enceval:build", "the ResNet encoder's eval-mode BatchNorm / ReLU / residual / max-pool glue"),
     Library("decb", 1, "decb:build", "the depth decoder's glue with the convolutions' biases folded in"),
     Library("wrw", 1, "wrw:build", "the weight gradient of the depth decoder's low-channel 3x3 convolutions"),

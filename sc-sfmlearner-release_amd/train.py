@@ -18,8 +18,12 @@ Differences from the reference, all forced by the platform or by the scale-out d
     (same files and columns as the reference) and to stdout; with `--log-output` the validation pictures are
     made on the GPU (scsfm_hip/validation_log.py) and written as PNG files under `<save_path>/valid/0..2`.
   * `torch.autograd.set_detect_anomaly(True)` (train.py:67) is not enabled: the kernels are NaN-free.
+  * `--shard-validation` (extension): every rank validates the batches it owns (scsfm_hip.validation.owner), each
+    batch's result stays in a table on the device and the pass is reduced once at its end; without it rank 0 validates
+    alone, as the reference's single process does.
 """
 import argparse
+import contextlib
 import csv
 import datetime
 import os
@@ -99,6 +103,9 @@ parser.add_argument('--exact-mask-normalisation', action='store_true',
                     help='data parallel: all-reduce the mask sums so the loss equals the single-process loss on the global batch. '
                          '(BatchNorm running statistics stay per rank either way -- as per replica under the reference\'s '
                          'nn.DataParallel, train.py:168-169 -- and rank 0\'s are the ones validated and checkpointed.)')
+parser.add_argument('--shard-validation', action='store_true',
+                    help='split the validation pass over the data-parallel ranks by whole batches and keep every batch\'s '
+                         'result on the device until the end of the pass (same averages for every number of ranks)')
 
 best_error = -1
 n_iter = 0
@@ -230,8 +237,13 @@ def main():
     train_loader = torch.utils.data.DataLoader(train_set, batch_size=args.batch_size, shuffle=train_sampler is None,
                                                sampler=train_sampler, num_workers=args.workers, pin_memory=True,
                                                drop_last=world > 1)
-    val_loader = torch.utils.data.DataLoader(val_set, batch_size=args.batch_size, shuffle=False,
-                                             num_workers=args.workers, pin_memory=True)
+    if args.shard_validation:
+        # whole batches of the unsharded loader, dealt to the ranks; those --log-output pictures stay with rank 0's writers
+        owned = hip_validation.OwnedBatches(len(val_set), args.batch_size, rank, world, pinned=3 if args.log_output else 0)
+        val_loader = torch.utils.data.DataLoader(val_set, batch_sampler=owned, num_workers=args.workers, pin_memory=True)
+    else:
+        val_loader = torch.utils.data.DataLoader(val_set, batch_size=args.batch_size, shuffle=False,
+                                                 num_workers=args.workers, pin_memory=True)
     if args.epoch_size == 0:
         args.epoch_size = len(train_loader)
 
@@ -284,12 +296,15 @@ def main():
         if is_main:
             logger.train_writer.write(' * Avg Loss : {:.3f}'.format(train_loss))
 
-        # validation and checkpoints on rank 0 (the nets are identical on every rank after the step)
-        if is_main:
+        # validation and checkpoints on rank 0 (the nets are identical on every rank after the step); with
+        # --shard-validation every rank validates its batches and all of them hold the pass's averages
+        if is_main or args.shard_validation:
             logger.reset_valid_bar()
             d_net = disp_net.module if world > 1 else disp_net
             p_net = pose_net.module if world > 1 else pose_net
-            errors, error_names = validate(args, val_loader, d_net, p_net, epoch, logger, output_writers)
+            with rank0_statistics((d_net, p_net), world if args.shard_validation else 1):
+                errors, error_names = validate(args, val_loader, d_net, p_net, epoch, logger, output_writers, verbose=is_main)
+        if is_main:
             logger.valid_writer.write(' * Avg {}'.format(', '.join('{} : {:.3f}'.format(n, e) for n, e in zip(error_names, errors))))
             for error, name in zip(errors, error_names):
                 training_writer.add_scalar(name, error, epoch)
@@ -334,6 +349,27 @@ def wrap_ddp(net, local_rank=None):
     ddp = torch.nn.parallel.DistributedDataParallel
     ids = [local_rank] if (local_rank is not None and next(net.parameters()).is_cuda) else None
     return ddp(net, device_ids=ids, bucket_cap_mb=64, gradient_as_bucket_view=True, broadcast_buffers=False)
+
+
+@contextlib.contextmanager
+def rank0_statistics(nets, world):
+    """For the length of a validation pass that every rank takes part in, all ranks hold rank 0's buffers.  The
+    parameters are the same everywhere after a step, but the BatchNorm running statistics are per rank (``wrap_ddp``) and
+    rank 0's are the ones validated and checkpointed: with them a batch gives the same result whichever rank owns it.
+    Every rank gets its own statistics back afterwards, so training goes on as without the pass."""
+    if world == 1:
+        yield
+        return
+    buffers = [b for net in nets for b in net.buffers()]
+    own = [b.clone() for b in buffers]
+    for b in buffers:
+        torch.distributed.broadcast(b, 0)
+    try:
+        yield
+    finally:
+        with torch.no_grad():
+            for b, saved in zip(buffers, own):
+                b.copy_(saved)
 
 
 def train_step(args, disp_net, pose_net, optimizer, tgt_img, ref_imgs, intrinsics):
@@ -422,18 +458,33 @@ def train(args, train_loader, disp_net, pose_net, optimizer, epoch_size, logger,
     return losses.avg[0]
 
 
-def validate(args, val_loader, disp_net, pose_net, epoch, logger, output_writers=[]):
+def validate(args, val_loader, disp_net, pose_net, epoch, logger, output_writers=[], verbose=True):
     """One validation pass of main() (train.py:206-209 of the reference): against ground truth with --with-gt, the
-    losses otherwise; the writers of --log-output go to whichever runs."""
+    losses otherwise; the writers of --log-output go to whichever runs.  ``verbose=False`` (the ranks other than 0 of a
+    sharded pass) keeps the loop from writing progress lines."""
+    quiet = {} if verbose else {'verbose': False}
     if args.with_gt:
-        return validate_with_gt(args, val_loader, disp_net, epoch, logger, output_writers)
-    return validate_without_gt(args, val_loader, disp_net, pose_net, epoch, logger, output_writers)
+        return validate_with_gt(args, val_loader, disp_net, epoch, logger, output_writers, **quiet)
+    return validate_without_gt(args, val_loader, disp_net, pose_net, epoch, logger, output_writers, **quiet)
+
+
+def validation_plan(args, val_loader):
+    """-> (the global number of every batch ``val_loader`` yields, the table of the pass or None).  Without
+    --shard-validation the loader yields every batch and there is no table: the loops average on the host as the
+    reference does.  With it the loader yields the batches this rank owns (scsfm_hip.validation.OwnedBatches; any other
+    loader is taken as a whole pass) and every batch's result goes into its row of a ValidationTable on the device."""
+    if not getattr(args, 'shard_validation', False):
+        return range(len(val_loader)), None
+    owned = getattr(val_loader, 'batch_sampler', None)
+    if isinstance(owned, hip_validation.OwnedBatches):
+        return owned.indices, hip_validation.ValidationTable(owned.n_batches, device)
+    return range(len(val_loader)), hip_validation.ValidationTable(len(val_loader), device)
 
 
 @torch.no_grad()
-def validate_without_gt(args, val_loader, disp_net, pose_net, epoch, logger, output_writers=[]):
+def validate_without_gt(args, val_loader, disp_net, pose_net, epoch, logger, output_writers=[], verbose=True):
     """Photometric / smoothness / geometry losses on the validation split, auto-mask off
-    (train.py:302-362)."""
+    (train.py:302-362).  ``i`` is the batch's number in the whole pass, ``k`` its number among this rank's."""
     global device
     batch_time = AverageMeter()
     losses = AverageMeter(i=4, precision=4)
@@ -441,7 +492,8 @@ def validate_without_gt(args, val_loader, disp_net, pose_net, epoch, logger, out
     pose_net.eval()
     end = time.time()
     logger.valid_bar.update(0)
-    for i, (tgt_img, ref_imgs, intrinsics, intrinsics_inv) in enumerate(val_loader):
+    indices, table = validation_plan(args, val_loader)
+    for k, (i, (tgt_img, ref_imgs, intrinsics, intrinsics_inv)) in enumerate(zip(indices, val_loader)):
         tgt_img = tgt_img.to(device)
         ref_imgs = [img.to(device) for img in ref_imgs]
         intrinsics = intrinsics.to(device).float()
@@ -455,20 +507,27 @@ def validate_without_gt(args, val_loader, disp_net, pose_net, epoch, logger, out
         loss_1, loss_3 = compute_photo_and_geometry_loss(tgt_img, ref_imgs, intrinsics, tgt_depth, ref_depths, poses, poses_inv,
                                                          args.num_scales, args.with_ssim, args.with_mask, False, args.padding_mode)
         loss_2 = compute_smooth_loss(tgt_depth, tgt_img, ref_depths, ref_imgs)
-        losses.update([float(loss_1), float(loss_1), float(loss_2), float(loss_3)])
+        if table is None:
+            losses.update([float(loss_1), float(loss_1), float(loss_2), float(loss_3)])
+        else:  # the same list into row i of the table, by one library call and without a read-back
+            table.add_losses(i, loss_1, loss_2, loss_3)
         batch_time.update(time.time() - end)
         end = time.time()
-        logger.valid_bar.update(i + 1)
-        if i % args.print_freq == 0:
+        logger.valid_bar.update(k + 1)
+        if verbose and k % args.print_freq == 0:
+            if table is not None:
+                val, avg = table.peek(i)
+                losses.val, losses.avg = val[:4], avg[:4]
             logger.valid_writer.write('valid: Time {} Loss {}'.format(batch_time, losses))
     logger.valid_bar.update(len(val_loader))
-    return losses.avg, ['Total loss', 'Photo loss', 'Smooth loss', 'Consistency loss']
+    names = ['Total loss', 'Photo loss', 'Smooth loss', 'Consistency loss']
+    return (losses.avg if table is None else table.finish()[0][:len(names)]), names
 
 
 @torch.no_grad()
-def validate_with_gt(args, val_loader, disp_net, epoch, logger, output_writers=[]):
+def validate_with_gt(args, val_loader, disp_net, epoch, logger, output_writers=[], verbose=True):
     """Depth metrics against ground truth; errors[1] (abs_rel) selects the best model
-    (train.py:365-423)."""
+    (train.py:365-423).  ``i`` is the batch's number in the whole pass, ``k`` its number among this rank's."""
     global device
     batch_time = AverageMeter()
     error_names = ['abs_diff', 'abs_rel', 'sq_rel', 'a1', 'a2', 'a3']
@@ -476,10 +535,11 @@ def validate_with_gt(args, val_loader, disp_net, epoch, logger, output_writers=[
     disp_net.eval()
     end = time.time()
     logger.valid_bar.update(0)
-    for i, (tgt_img, depth) in enumerate(val_loader):
+    indices, table = validation_plan(args, val_loader)
+    for k, (i, (tgt_img, depth)) in enumerate(zip(indices, val_loader)):
         tgt_img = tgt_img.to(device)
         depth = depth.to(device)
-        if depth.nelement() == 0:
+        if depth.nelement() == 0:  # (with a table: the batch's row stays absent)
             continue
         output_disp = disp_net(tgt_img)
         if i < len(output_writers):  # (train.py:390-408; the ground truth is shown without the in-place write of :397)
@@ -492,14 +552,20 @@ def validate_with_gt(args, val_loader, disp_net, epoch, logger, output_writers=[
                                                                             'magma', None, floats=False)[1][0], epoch)
             log_disparity(output_writers[i], output_disp[0], 1 / output_disp[:1, 0], epoch)
         # 1 / disp, the nearest resize to the ground truth's size and compute_errors' per-image loop: one library call
-        errors.update(hip_validation.batch_mean(hip_validation.depth_errors(depth, output_disp, args.dataset, is_disp=True)))
+        if table is None:
+            errors.update(hip_validation.batch_mean(hip_validation.depth_errors(depth, output_disp, args.dataset, is_disp=True)))
+        else:  # the same call, which also leaves the batch's mean in row i of the table: no read-back
+            table.add_errors(i, depth, output_disp, args.dataset, is_disp=True)
         batch_time.update(time.time() - end)
         end = time.time()
-        logger.valid_bar.update(i + 1)
-        if i % args.print_freq == 0:
+        logger.valid_bar.update(k + 1)
+        if verbose and k % args.print_freq == 0:
+            if table is not None:
+                val, avg = table.peek(i)
+                errors.val, errors.avg = val[:6], avg[:6]
             logger.valid_writer.write('valid: Time {} Abs Error {:.4f} ({:.4f})'.format(batch_time, errors.val[0], errors.avg[0]))
     logger.valid_bar.update(len(val_loader))
-    return errors.avg, error_names
+    return (errors.avg if table is None else table.finish()[0][:len(error_names)]), error_names
 
 
 def compute_depth(disp_net, tgt_img, ref_imgs):
