@@ -20,6 +20,10 @@ ODD_UP = [(1, 3, 2, 1, 1), (1, 5, 0, 2, 3), (2, 7, 3, 3, 5), (1, 4, 4, 5, 131)]
 CHUNK_PAD = [(1, 1, 2, 2), (1, 2, 3, 3)] + [(1, 1, 2, W) for W in (254, 255, 256, 257, 258)] + \
     [(2, 3, 3, 258), (3, 2, 5, 513)]
 CHUNK_UP = [s for W in (127, 128, 129, 255, 256, 257) for s in ((1, 1, 1, 1, W), (1, 2, 0, 2, W))] + [(2, 3, 2, 5, 131)]
+# DispResNet(50) on a 2 x 3 x 64 x 128 image: the pad input f4 and up_cat_pad at levels 4..0, with skips of 1024, 512
+# and 256 channels
+R50_PAD = [(2, 2048, 2, 4)]
+R50_UP = [(2, 256, 1024, 2, 4), (2, 128, 512, 4, 8), (2, 64, 256, 8, 16), (2, 32, 64, 16, 32), (2, 16, 0, 32, 64)]
 
 FLT_MIN, DENORM = np.float32(2.0 ** -126), np.float32(2.0 ** -149)
 SPECIALS = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, DENORM, -DENORM, FLT_MIN, -FLT_MIN, -1e-8, -17.5, -88.0,

@@ -23,6 +23,40 @@ STAGE_SHAPES = [(12, 64, 128, 416), (12, 64, 64, 208), (12, 128, 32, 104), (12, 
 ODD_SHAPES = [(1, 3, 2, 2), (2, 5, 3, 3), (3, 2, 5, 263), (1, 4, 7, 131)]
 EPS, MOMENTUM = 1e-5, 0.1
 
+# How csrc_enc/scsfm_encoder.hip splits a channel: S = min(ceil(kTargetBlocks / C), ceil(units / kThreads), kMaxSplit)
+# workgroups, units = B * H * W / V with V = 4 on the 16-byte path (H * W a multiple of 4), else 1.  The shapes below are
+# listed with the S they are meant to hit; splits() recomputes it from the constants in the source, so that a change
+# there cannot quietly take a case off its edge.
+# ResNet-50's stage outputs (256 ... 2048 channels) at batch 2, sized for the splits S = 8, 4, 2, 1
+R50_STAGE_SHAPES = {(2, 256, 32, 128): 8, (2, 512, 32, 64): 4, (2, 1024, 16, 52): 2, (2, 2048, 8, 26): 1}
+# the cap; a split that is no power of two and above 32; uneven ranges with the batch boundaries (units 401, 802) inside
+# a range on the 16-byte path; uneven ranges on the scalar path
+SPLIT_EDGE_SHAPES = {(1, 3, 128, 512): 64, (2, 48, 128, 172): 43, (3, 4, 4, 401): 5, (1, 2, 5, 127): 3}
+# those the host simulator runs in under a second a case; S = 43 needs 48 channels of more than 42 * 256 units each, 2 M
+# entries, which take it 4 to 8 s a case: that one runs on the GPU only
+HOSTSIM_SPLIT_EDGE_SHAPES = [(1, 3, 128, 512), (3, 4, 4, 401), (1, 2, 5, 127)]
+
+
+def kernel_constants():
+    """kTargetBlocks, kMaxSplit, kThreads as csrc_enc/scsfm_encoder.hip defines them"""
+    import os
+    import re
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sc-sfmlearner-release_amd",
+                       "csrc_enc", "scsfm_encoder.hip")
+    with open(src) as f:
+        text = f.read()
+    return tuple(int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
+                 for name in ("kTargetBlocks", "kMaxSplit", "kThreads"))
+
+
+def splits(shape, aligned=True):
+    """-> (S, vec) for a contiguous tensor of ``shape``: splits() and the 16-byte condition of the source, in Python"""
+    target, most_split, threads = kernel_constants()
+    B, C, H, W = shape
+    vec = (H * W) % 4 == 0 and aligned
+    units = B * (H * W // 4 if vec else H * W)
+    return max(1, min(-(-target // C), -(-units // threads), most_split)), vec
+
 
 def make_case(shape, mode, seed, device="cpu"):
     """x, identity (mode 2), gamma (with negative entries and a zero one), beta, running statistics, the upstream
@@ -141,23 +175,46 @@ def pool_input(shape, seed, device="cpu"):
 KINK_MARGIN = 3e-4
 
 
-def _relu_sites(enc64, x):
-    """The ReLU sites of ResnetEncoder(18)'s chain in order, evaluated functionally (no buffer is touched): yields
-    (the convolution whose output channels feed the site, the pre-activation, the ReLU output if a max-pool reads it)."""
-    e = enc64.encoder
-    bn = lambda m, t: F.batch_norm(t, None, None, m.weight, m.bias, True, 0.0, m.eps)  # noqa: E731
-    v = bn(e.bn1, e.conv1(x))
+def _bn(m, t):
+    """training-mode BatchNorm by the module's parameters, functionally: no buffer is touched"""
+    return F.batch_norm(t, None, None, m.weight, m.bias, True, 0.0, m.eps)
+
+
+def _block_sites(b, x):
+    """The ReLU sites of one residual block on the input ``x``: a BasicBlock's two (conv1; conv2 with the identity
+    added) or a Bottleneck's three (conv1; conv2; conv3 with the identity added).  The down-sample BatchNorm has no ReLU
+    behind it (mode 0) and is no site.  Yields as _relu_sites does; the generator's return value is the block's output."""
+    identity = x if b.downsample is None else _bn(b.downsample[1], b.downsample[0](x))
+    v = _bn(b.bn1, b.conv1(x))
+    yield b.conv1, v, None
+    if hasattr(b, "conv3"):
+        v = _bn(b.bn2, b.conv2(F.relu(v)))
+        yield b.conv2, v, None
+        v = _bn(b.bn3, b.conv3(F.relu(v))) + identity
+        yield b.conv3, v, None
+    else:
+        v = _bn(b.bn2, b.conv2(F.relu(v))) + identity
+        yield b.conv2, v, None
+    return F.relu(v)
+
+
+def block_sites(block, x):
+    """the sites function of a single BasicBlock or Bottleneck (for condition_encoder and preactivation_errors)"""
+    yield from _block_sites(block, x)
+
+
+def _relu_sites(enc, x):
+    """The ReLU sites of a ResnetEncoder's chain in order (ResNet-18: 17, ResNet-50: 49), evaluated functionally in the
+    dtype of ``enc`` and ``x`` (no buffer is touched): yields (the convolution whose output channels feed the site, the
+    pre-activation, the ReLU output if a max-pool reads it)."""
+    e = enc.encoder
+    v = _bn(e.bn1, e.conv1(x))
     f0 = F.relu(v)
     yield e.conv1, v, f0
     x = F.max_pool2d(f0, 3, 2, 1)
     for layer in (e.layer1, e.layer2, e.layer3, e.layer4):
         for b in layer:
-            identity = x if b.downsample is None else bn(b.downsample[1], b.downsample[0](x))
-            v = bn(b.bn1, b.conv1(x))
-            yield b.conv1, v, None
-            v = bn(b.bn2, b.conv2(F.relu(v))) + identity
-            yield b.conv2, v, None
-            x = F.relu(v)
+            x = yield from _block_sites(b, x)
 
 
 def _channels_on_a_kink(v, pooled_from, margin):
@@ -170,15 +227,16 @@ def _channels_on_a_kink(v, pooled_from, margin):
     return bad
 
 
-def condition_encoder(enc64, xs, seed, margin=KINK_MARGIN, max_rounds=20000):
-    """Re-draws convolution output channels of the fp64 ResnetEncoder(18) ``enc64`` (fp32-representable values, seeded)
-    until no ReLU pre-activation and no pooling gap of its training-mode chain lies in (0, margin) for any input in
-    ``xs``.  -> (rounds used, smallest non-zero |pre-activation|, smallest non-zero pooling gap)."""
+def condition_encoder(enc64, xs, seed, margin=KINK_MARGIN, max_rounds=20000, sites=_relu_sites):
+    """Re-draws convolution output channels of the fp64 ``enc64`` -- a ResnetEncoder(18), or with ``sites=block_sites`` a
+    single BasicBlock or Bottleneck -- (fp32-representable values, seeded) until no ReLU pre-activation and no pooling
+    gap of its training-mode chain lies in (0, margin) for any input in ``xs``.  -> (rounds used, smallest non-zero
+    |pre-activation|, smallest non-zero pooling gap; inf where there is no pooling)."""
     gen = torch.Generator(device=xs[0].device).manual_seed(seed)
     with torch.no_grad():
         for rounds in range(max_rounds):
             lo_v, lo_gap, clean = float("inf"), float("inf"), True
-            for group in zip(*[_relu_sites(enc64, x) for x in xs]):
+            for group in zip(*[sites(enc64, x) for x in xs]):
                 conv = group[0][0]
                 bad = torch.zeros(conv.weight.shape[0], dtype=torch.bool, device=conv.weight.device)
                 for _, v, pooled_from in group:
@@ -200,3 +258,21 @@ def condition_encoder(enc64, xs, seed, margin=KINK_MARGIN, max_rounds=20000):
             if clean:
                 return rounds, lo_v, lo_gap
     raise AssertionError("could not move the encoder off its kinks")
+
+
+def preactivation_errors(m32, m64, xs, sites=_relu_sites):
+    """max|v32 - v64| of the pre-activation at every ReLU site, in the sites' order, over the inputs ``xs`` (fp32): the
+    ATen chain of ``sites`` evaluated functionally in fp32 through ``m32`` and in fp64 through ``m64``, which holds the
+    same values.  A reference quantity: the fused path takes no part in it."""
+    with torch.no_grad():
+        errs = None
+        for x in xs:
+            pairs = zip(sites(m32, x), sites(m64, x.double()))
+            e = [float((a[1].double() - b[1]).abs().max()) for a, b in pairs]
+            errs = e if errs is None else [max(p, q) for p, q in zip(errs, e)]
+    return errs
+
+
+def preactivation_error(m32, m64, xs, sites=_relu_sites):
+    """the largest entry of preactivation_errors: what KINK_MARGIN has to stay well above"""
+    return max(preactivation_errors(m32, m64, xs, sites))

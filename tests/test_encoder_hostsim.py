@@ -36,8 +36,14 @@ def _run(case, n_forward=1):
 
 @pytest.mark.parametrize("order", ["forward", "reverse"])
 @pytest.mark.parametrize("mode", [0, 1, 2])
-@pytest.mark.parametrize("shape", R.ODD_SHAPES + REDUCED)
+@pytest.mark.parametrize("shape", R.ODD_SHAPES + REDUCED + R.HOSTSIM_SPLIT_EDGE_SHAPES)
 def test_bn_act_meets_the_contract(shape, mode, order, monkeypatch):
+    """The last three shapes are edges of the split of a channel over S workgroups (tests/_encoder_ref.py): the cap
+    S = 64, and the uneven S = 5 (16-byte path, batch boundaries inside a range) and S = 3 (scalar path).  The S = 43
+    shape (2, 48, 128, 172) takes the simulator 4 to 8 s a case and runs on the GPU only
+    (tests/test_gpu_encoder_fused.py)."""
+    if shape in R.SPLIT_EDGE_SHAPES:
+        assert R.splits(shape)[0] == R.SPLIT_EDGE_SHAPES[shape]
     case = R.make_case(shape, mode, seed=sum(shape) + mode)
     monkeypatch.delenv("HOSTSIM_ORDER", raising=False)
     first = _run(case)
@@ -51,6 +57,23 @@ def test_bn_act_meets_the_contract(shape, mode, order, monkeypatch):
         fused = first
     R.check_contract(f"hostsim {R.MODES[mode]} {shape}", fused, R.aten_chain(case, torch.float32),
                      R.aten_chain(case, torch.float64))
+
+
+def test_split_cases_hit_the_intended_values():
+    """the S of every listed shape, recomputed from the constants of csrc_enc/scsfm_encoder.hip: all of 1, 2, 3, 4, 5, 8,
+    43 and 64, the uneven ones on both paths"""
+    listed = {**R.R50_STAGE_SHAPES, **R.SPLIT_EDGE_SHAPES}
+    got = {shape: R.splits(shape) for shape in listed}
+    assert {shape: S for shape, (S, _) in got.items()} == listed
+    assert sorted(set(listed.values())) == [1, 2, 3, 4, 5, 8, 43, 64]
+    assert [shape for shape, (_, vec) in got.items() if not vec] == [(1, 2, 5, 127)]
+    assert set(R.HOSTSIM_SPLIT_EDGE_SHAPES) == set(R.SPLIT_EDGE_SHAPES) - {(2, 48, 128, 172)}
+    for (B, C, H, W), (S, vec) in got.items():  # uneven: the ranges of units are not all of one length
+        units = B * H * W // (4 if vec else 1)
+        assert (units % S != 0) == (S in (3, 5)), (B, C, H, W)
+    # (3, 4, 4, 401): the batch boundaries at units 401 and 802 lie inside ranges, not between them
+    cuts = [1203 * s // 5 for s in range(6)]
+    assert 401 not in cuts and 802 not in cuts
 
 
 @pytest.mark.parametrize("mode", [1, 2])

@@ -10,15 +10,16 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _decoder_ref as R
 from _util import report
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 ELU_SHAPES = [(B, C, H, W) for B, C, H in itertools.product((1, 2), (1, 3, 5), (2, 3, 5))
-              for W in (2, 3, 254, 255, 256, 257, 258, 513)]
+              for W in (2, 3, 254, 255, 256, 257, 258, 513)] + R.R50_PAD + [(2, 256, 4, 8)]  # (... and channel-sized)
 UP_SHAPES = [(B, Ca, Cs, H, W) for B, (Ca, Cs), H in itertools.product((1, 2), ((1, 0), (3, 2), (5, 0)), (1, 2, 3))
-             for W in (2, 3, 127, 128, 129)]
+             for W in (2, 3, 127, 128, 129)] + R.R50_UP  # (... and the levels under ResNet-50's skips)
 HEAD_SHAPES = [(B, 1, H, W) for B in (1, 2) for H, W in ((2, 2), (5, 51), (1, 255), (16, 16), (1, 257))] + \
     [(2, 3, 1, 257), (2, 1, 64, 208)]
 

@@ -116,14 +116,14 @@ def run_up(B, Ca, Cs, H, W, seed):
     return worst
 
 
-@pytest.mark.parametrize("shape", LEVELS_PAD + ODD_PAD)
+@pytest.mark.parametrize("shape", LEVELS_PAD + ODD_PAD + R.R50_PAD)
 @pytest.mark.parametrize("elu", [False, True])
 def test_pad_matches_aten(shape, elu):
     worst = run_pad(*shape, elu, seed=sum(shape) + elu)
     report(f"decoder pad elu={int(elu)} {shape}: corner entries at {worst:.3f} of their bound")
 
 
-@pytest.mark.parametrize("shape", LEVELS_UP + ODD_UP)
+@pytest.mark.parametrize("shape", LEVELS_UP + ODD_UP + R.R50_UP)
 def test_up_cat_pad_matches_aten(shape):
     worst = run_up(*shape, seed=sum(shape))
     report(f"decoder up_cat_pad {shape}: corner entries at {worst:.3f} of their bound")
@@ -300,3 +300,118 @@ def test_disp_resnet_gradients_within_the_reference_spread(num_scales, determini
         assert d <= 3 * spread + 1e-5 * scale, (tuple(g.shape), d, spread, scale)
     report(f"DispResNet gradients num_scales={num_scales}: fused vs reference worst {worst_rel:.2e} of scale, "
            f"reference vs reference {worst_spread:.2e}")
+
+
+# ---- the decoder under ResNet-50's encoder: skips of 256, 512 and 1024 channels, f4 of 2048 ----------------------------
+@pytest.fixture(scope="module")
+def resnet50_decoder():
+    """DispResNet(50)'s decoder in training mode and the encoder's five features of a 2 x 3 x 64 x 128 image, detached:
+    the comparison starts behind the encoder (whose fp32 error at this depth is
+    test_gpu_encoder_fused.test_resnet50_encoder_takes_the_fused_path's subject)"""
+    import models
+    torch.manual_seed(2)
+    net = models.DispResNet(50, False).to(DEV).train()
+    x = torch.randn(2, 3, 64, 128, device=DEV, generator=torch.Generator(device=DEV).manual_seed(3))
+    with torch.no_grad():
+        feats = [f.clone() for f in net.encoder(x)]
+    assert [tuple(f.shape) for f in feats] == [(2, 64, 32, 64), (2, 256, 16, 32), (2, 512, 8, 16), (2, 1024, 4, 8),
+                                               (2, 2048, 2, 4)]
+    return net.decoder, feats
+
+
+PATHS = ["forward_fused", "forward_fused_bias"]
+
+
+@pytest.mark.parametrize("path", PATHS)
+def test_resnet50_decoder_outputs_match_the_reference(path, resnet50_decoder, deterministic_miopen):
+    """as test_disp_resnet_outputs_match_the_reference, for both fused paths; forward() takes the folded-bias one"""
+    dec, feats = resnet50_decoder
+    assert dec.fused_path_applies(feats) and dec.bias_path_applies()
+    ref1 = dec.forward_reference(feats)
+    got = getattr(dec, path)(feats)
+    ref2 = dec.forward_reference(feats)
+    top = dec(feats)
+    assert len(got) == len(top) == len(ref1) == 4
+    assert [tuple(o.shape) for o in got] == [(2, 1, 64 >> s, 128 >> s) for s in range(4)]
+    reproducible = all(same_bits(a, b) for a, b in zip(ref1, ref2))
+    for s, (a, b, c, t) in enumerate(zip(got, ref1, ref2, top)):
+        if reproducible:
+            assert same_bits(a, b) and same_bits(t, b), f"scale {s}"
+        else:
+            assert float((a - b).abs().max()) <= 3 * float((c - b).abs().max()), f"scale {s}"
+    report(f"DepthDecoder under ResNet-50 {path}: reference reproducible {reproducible}, fused bit-identical "
+           f"{all(same_bits(a, b) for a, b in zip(got, ref1))}")
+
+
+@pytest.mark.parametrize("num_scales", [1, 4])
+@pytest.mark.parametrize("path", PATHS)
+def test_resnet50_decoder_gradients_within_the_reference_spread(path, num_scales, resnet50_decoder,
+                                                                deterministic_miopen):
+    """Gradients of a loss over the first num_scales outputs with respect to the decoder's parameters and the five
+    features: fused against the reference, next to two reference runs against each other."""
+    dec, feats = resnet50_decoder
+    w = [torch.randn(2, 1, 64 >> s, 128 >> s, device=DEV, generator=torch.Generator(device=DEV).manual_seed(10 + s))
+         for s in range(4)]
+
+    def grads(forward):
+        dec.zero_grad(set_to_none=True)
+        leaves = [f.clone().requires_grad_() for f in feats]
+        outs = forward(leaves)
+        sum((o * w[s]).sum() for s, o in enumerate(outs[:num_scales])).backward()
+        out = {f"feature {i}": f.grad for i, f in enumerate(leaves)}
+        out.update({n: p.grad.clone() for n, p in dec.named_parameters() if p.grad is not None})
+        return out
+
+    ref1, ref2, got = grads(dec.forward_reference), grads(dec.forward_reference), grads(getattr(dec, path))
+    assert list(got) == list(ref1) and len(got) == 5 + 2 * (10 + num_scales)
+    worst_rel, worst_spread = 0.0, 0.0
+    for n in got:
+        g, r1, r2 = got[n], ref1[n], ref2[n]
+        assert g is not None and g.shape == r1.shape, n
+        scale = float(r1.abs().max()) + 1e-30
+        d = float((g - r1).abs().max())
+        spread = float((r2 - r1).abs().max())
+        worst_rel = max(worst_rel, d / scale)
+        worst_spread = max(worst_spread, spread / scale)
+        assert d <= 3 * spread + 1e-5 * scale, (n, tuple(g.shape), d, spread, scale)
+    report(f"DepthDecoder under ResNet-50 {path} num_scales={num_scales}: fused vs reference worst {worst_rel:.2e} of "
+           f"scale, reference vs reference {worst_spread:.2e}")
+
+
+def test_resnet50_decoder_routes_the_layers_resnet18s_does(resnet50_decoder, monkeypatch):
+    """The decoder's own channel counts do not depend on the encoder, so scsfm_hip.conv_wrw and scsfm_hip.decoder_dgrad
+    take the same convolutions (by their index in DepthDecoder.decoder) under ResNet-50's features as under
+    ResNet-18's, on both fused paths."""
+    import models
+    from scsfm_hip import conv_wrw as CW, decoder_dgrad as DG
+    dec50, feats50 = resnet50_decoder
+    torch.manual_seed(2)
+    dec18 = models.DispResNet(18, False).decoder.to(DEV).train()
+    feats18 = [torch.randn(f.shape[0], c, *f.shape[2:], device=DEV) for f, c in zip(feats50, dec18.num_ch_enc)]
+    seen = []
+    real_wrw, real_tail = CW.applies, DG.applies
+
+    def wrw_applies(x, m):
+        seen.append(("wrw", id(m), real_wrw(x, m)))
+        return seen[-1][2]
+
+    def tail_applies(b, bias, head):
+        seen.append(("tail", id(head), real_tail(b, bias, head)))
+        return seen[-1][2]
+
+    monkeypatch.setattr(CW, "applies", wrw_applies)
+    monkeypatch.setattr(DG, "applies", tail_applies)
+
+    def routes(dec, feats, path):
+        index = {id(dec._conv(k)): k for k in range(len(dec.decoder))}
+        del seen[:]
+        with torch.no_grad():
+            getattr(dec, path)(feats)
+        return [(kind, index[m], took) for kind, m, took in seen]
+
+    for path in PATHS:
+        r18, r50 = routes(dec18, feats18, path), routes(dec50, feats50, path)
+        assert r18 == r50, path
+        taken = sorted(k for kind, k, took in r50 if kind == "wrw" and took)
+        assert taken == [k for k in sorted(k for kind, k, _ in r50 if kind == "wrw") if k in (6, 7, 8, 9, 10, 11, 12)], path
+        assert len(taken) >= 6 and (path == "forward_fused" or ("tail", 10, True) in r50)
