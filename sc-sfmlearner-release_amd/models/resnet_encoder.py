@@ -33,6 +33,18 @@ def _EV():
     return _encoder_eval_ops
 
 
+_encoder_frozen_ops = None
+
+
+def _EF():
+    """scsfm_hip.encoder_frozen, imported on first use (a CPU-only run never loads it)"""
+    global _encoder_frozen_ops
+    if _encoder_frozen_ops is None:
+        from scsfm_hip import encoder_frozen
+        _encoder_frozen_ops = encoder_frozen
+    return _encoder_frozen_ops
+
+
 def _fused_applies(x, *bns):
     """CUDA fp32 contiguous NCHW activations through training-mode BatchNorms take the fused HIP glue
     (scsfm_hip.encoder); eval mode is ``_eval_applies``'s; CPU, fp64, channels_last and BatchNorms without affine
@@ -42,16 +54,29 @@ def _fused_applies(x, *bns):
 
 def _eval_applies(x, *bns):
     """CUDA fp32 contiguous NCHW activations through eval-mode BatchNorms with grad mode off take the fused eval-mode HIP
-    glue (scsfm_hip.encoder_eval); eval mode with grad enabled, SCSFM_EVAL_TORCH=1, CPU, fp64, channels_last and
-    BatchNorms without affine parameters or running statistics run the ATen chain unchanged."""
+    glue (scsfm_hip.encoder_eval); eval mode with grad enabled is ``_frozen_applies``'s where the module was frozen and
+    ATen's otherwise; SCSFM_EVAL_TORCH=1, CPU, fp64, channels_last and BatchNorms without affine parameters or running
+    statistics run the ATen chain unchanged."""
     return x.is_cuda and _EV().applies(x, *bns)
+
+
+def _frozen_applies(x, *bns, relu=True):
+    """CUDA fp32 contiguous NCHW activations with grad mode on through BatchNorms that scsfm_hip.encoder_frozen.freeze
+    holds in eval mode (train.py --freeze-bn) take the fused frozen-statistics HIP glue where a ReLU follows; a BatchNorm
+    without one (the down-sample branch: nothing to fuse, and measured slower), a module that is merely in eval
+    mode, SCSFM_FROZEN_TORCH=1, CPU, fp64 and channels_last run the ATen chain unchanged.  (The class is looked at only
+    once the module is known not to be in training mode: the ordinary step pays one attribute test.)"""
+    return x.is_cuda and not any(bn.training for bn in bns) and _EF().applies(x, *bns, relu=relu)
 
 
 def _bn_act(x, bn, act, identity=None):
     """act(bn(x) [+ identity]), fused when the call qualifies (act is the module's in-place ReLU, or None): by
-    scsfm_hip.encoder in training mode, else by scsfm_hip.encoder_eval in eval mode under no_grad, else ATen"""
+    scsfm_hip.encoder in training mode, else by scsfm_hip.encoder_frozen for a frozen module with grad mode on and a
+    ReLU behind it, else by scsfm_hip.encoder_eval in eval mode under no_grad, else ATen"""
     if _fused_applies(x, bn) and (identity is None or _fused_applies(identity)):
         return _E().bn_act(x, bn, identity, relu=act is not None)
+    if _frozen_applies(x, bn, relu=act is not None) and (identity is None or _frozen_applies(identity)):
+        return _EF().bn_act(x, bn, identity, relu=act is not None)
     if _eval_applies(x, bn) and (identity is None or _eval_applies(identity)):
         return _EV().bn_act(x, bn, identity, relu=act is not None)
     out = bn(x)
@@ -201,8 +226,10 @@ class ResnetEncoder(nn.Module):
     def forward(self, input_image):
         """The stem's BatchNorm / ReLU / max-pool and every block's BatchNorm / ReLU / residual add run as the fused HIP
         kernels of scsfm_hip.encoder where the call qualifies (``_fused_applies``: CUDA fp32 contiguous NCHW in training mode),
-        or of scsfm_hip.encoder_eval (``_eval_applies``: the same tensors in eval mode with grad mode off), through the same
-        modules' parameters and buffers; everything else is ``forward_reference``'s ATen chain."""
+        of scsfm_hip.encoder_frozen (``_frozen_applies``: the same tensors with grad mode on through modules that
+        ``freeze`` holds in eval mode; its stem is ``_bn_act`` followed by ``_maxpool``), or of scsfm_hip.encoder_eval
+        (``_eval_applies``: the same tensors in eval mode with grad mode off), through the same modules' parameters and
+        buffers; everything else is ``forward_reference``'s ATen chain."""
         e = self.encoder
         x = e.conv1(input_image)
         if _fused_applies(x, e.bn1) and _E().pool_applies(x):

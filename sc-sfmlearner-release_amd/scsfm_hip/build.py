@@ -31,7 +31,7 @@ import subprocess
 import sys
 import tempfile
 
-from .libraries import BY_NAME, HERE, INCLUDE, SUMMARY, TABLE
+from .libraries import BY_NAME, HERE, INCLUDE, LATER, SUMMARY, TABLE
 
 __doc__ = (__doc__ or "") + SUMMARY + "\n"
 
@@ -133,7 +133,7 @@ def build(force=False, verbose=True, extra=()):
 
 
 # Every other row, under its own names.
-for _row in TABLE[1:]:
+for _row in TABLE[1:] + LATER:
     globals().update({
         f"{_row.name.upper()}_CSRC": _row.csrc,
         f"{_row.name.upper()}_LIB": _row.lib,
@@ -188,7 +188,7 @@ def _build(lib, want, srcs, extra, force, verbose):
 
 
 if __name__ == "__main__":
-    for _row in TABLE:
+    for _row in TABLE + LATER:
         build_lib(_row.name, force="--force" in sys.argv)
-    for _row in TABLE:
+    for _row in TABLE + LATER:
         print(_row.lib)

@@ -10,8 +10,8 @@ training, for every path that runs a trained network under ``net.eval()`` and ``
 ``bn`` is an ``nn.BatchNorm2d`` in eval mode: its running statistics normalise, and they, the affine parameters and the
 batch counter are read, never written.  Eval-mode BatchNorm is a per-channel affine map, so every call is one launch
 without scratch, and there is no backward: these are plain functions that build no autograd node, and ``applies``
-demands that grad mode is off.  (Eval mode with grad enabled -- fine-tuning with frozen statistics -- keeps the ATen
-chain.)
+demands that grad mode is off.  (Eval mode with grad enabled keeps the ATen chain; fine-tuning with frozen statistics,
+train.py --freeze-bn, is scsfm_hip.encoder_frozen's, whose forward is this library's.)
 
 CUDA fp32 contiguous NCHW tensors only; ``applies`` says whether a call qualifies, and the models choose their path with
 it before calling in.  A missing library is an error (no eager fallback here).  Launches go on torch's current stream,

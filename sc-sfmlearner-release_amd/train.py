@@ -18,6 +18,8 @@ Differences from the reference, all forced by the platform or by the scale-out d
     (same files and columns as the reference) and to stdout; with `--log-output` the validation pictures are
     made on the GPU (scsfm_hip/validation_log.py) and written as PNG files under `<save_path>/valid/0..2`.
   * `torch.autograd.set_detect_anomaly(True)` (train.py:67) is not enabled: the kernels are NaN-free.
+  * `--freeze-bn stats|all` (extension): fine-tuning with the BatchNorm running statistics of the given weights held for
+    the whole run (scsfm_hip/encoder_frozen.py); `all` holds gamma and beta too.
   * `--shard-validation` (extension): every rank validates the batches it owns (scsfm_hip.validation.owner), each
     batch's result stays in a table on the device and the pass is reduced once at its end; without it rank 0 validates
     alone, as the reference's single process does.
@@ -44,6 +46,7 @@ except ImportError:
     compute_total_loss = None
 from scsfm_hip import config as hip_config
 from scsfm_hip import dist as hip_dist
+from scsfm_hip import encoder_frozen as hip_encoder_frozen
 from scsfm_hip import validation as hip_validation
 from scsfm_hip import validation_log as hip_validation_log
 from utils import save_checkpoint
@@ -106,6 +109,11 @@ parser.add_argument('--exact-mask-normalisation', action='store_true',
 parser.add_argument('--shard-validation', action='store_true',
                     help='split the validation pass over the data-parallel ranks by whole batches and keep every batch\'s '
                          'result on the device until the end of the pass (same averages for every number of ranks)')
+parser.add_argument('--freeze-bn', default='off', choices=['off', 'stats', 'all'],
+                    help='fine-tuning: stats = every BatchNorm of both nets normalises with the running statistics of the '
+                         'weights it was given for the whole run and never updates them (gamma and beta keep training); '
+                         'all = gamma and beta are held too; off = the reference\'s batch statistics.  Needs weights for '
+                         'both nets (--pretrained-disp / --pretrained-pose, or --with-pretrain 1)')
 
 best_error = -1
 n_iter = 0
@@ -180,6 +188,11 @@ def build_datasets(args):
 def main():
     global best_error, n_iter, device
     args = parser.parse_args()
+    unsourced = nets_without_statistics(args)
+    if unsourced:
+        parser.error("--freeze-bn {} would hold the initial running statistics (mean 0, variance 1) of {}: give it weights "
+                     "with {}, or --with-pretrain 1".format(args.freeze_bn, " and ".join(n for n, _ in unsourced),
+                                                            " / ".join(f for _, f in unsourced)))
     if args.with_pretrain:
         # the reference's default (--with-pretrain 1, train.py:53) downloads ImageNet weights; say so before any
         # dataset is crawled rather than from inside model construction
@@ -262,6 +275,13 @@ def main():
             print("=> using pre-trained weights for PoseResNet")
         pose_net.load_state_dict(torch.load(args.pretrained_pose, map_location=device)['state_dict'], strict=False)
 
+    if args.freeze_bn != 'off':
+        # after the weights are in place; before DDP looks at requires_grad and before the optimizer's lists are formed
+        frozen = [hip_encoder_frozen.freeze(net, affine=args.freeze_bn == 'all') for net in (disp_net, pose_net)]
+        if is_main:
+            print("=> --freeze-bn {}: {} + {} BatchNorm modules of DispResNet + PoseResNet normalise with their running "
+                  "statistics and never update them; gamma and beta {}".format(
+                      args.freeze_bn, frozen[0], frozen[1], "are held too" if args.freeze_bn == 'all' else "train"))
     if world > 1:
         # gradients: one bucketed all-reduce per step over RCCL / xGMI, overlapped with backward
         freeze_unused_scale_heads(disp_net, args.num_scales)
@@ -322,6 +342,15 @@ def main():
     logger.epoch_bar.finish()
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def nets_without_statistics(args):
+    """--freeze-bn holds the running statistics a net starts with, so each net needs a source of them: its own checkpoint
+    or the ImageNet weights.  -> [(the net's name, the flag that would give it weights)] for those that have none."""
+    if args.freeze_bn == 'off' or args.with_pretrain:
+        return []
+    return [(name, flag) for name, flag, path in (("DispResNet", "--pretrained-disp", args.pretrained_disp),
+                                                   ("PoseResNet", "--pretrained-pose", args.pretrained_pose)) if not path]
 
 
 def freeze_unused_scale_heads(disp_net, num_scales):
