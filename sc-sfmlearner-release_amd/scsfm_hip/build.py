@@ -31,7 +31,7 @@ import subprocess
 import sys
 import tempfile
 
-from .libraries import BY_NAME, HERE, INCLUDE, LATER, SUMMARY, TABLE
+from .libraries import BY_NAME, HERE, INCLUDE, LATER, ROWS, SUMMARY, TABLE, find  # noqa: F401  (LATER: as before)
 
 __doc__ = (__doc__ or "") + SUMMARY + "\n"
 
@@ -50,11 +50,11 @@ ID_MARKER = b"scsfm-source-id:"
 
 
 def lib_sources(name):
-    return sorted(glob.glob(os.path.join(BY_NAME[name].csrc, "*.hip")))
+    return sorted(glob.glob(os.path.join(find(name).csrc, "*.hip")))
 
 
 def lib_deps(name):
-    row = BY_NAME[name]
+    row = find(name)
     return lib_sources(name) + sorted(glob.glob(os.path.join(row.csrc, "*.h"))) + [row.header]
 
 
@@ -92,7 +92,7 @@ def binary_source_id(path=LIB):
 
 def lib_is_stale(name):
     """True when the in-tree library is missing or was built from other sources / flags than the tree's."""
-    return binary_source_id(BY_NAME[name].lib) != lib_source_id(name)
+    return binary_source_id(find(name).lib) != lib_source_id(name)
 
 
 def build_lib(name, force=False, verbose=True):
@@ -102,7 +102,7 @@ def build_lib(name, force=False, verbose=True):
     compiles)."""
     if not name:
         return build(force, verbose)  # (the loss library includes nothing from include/ by name: no -I)
-    return _build(BY_NAME[name].lib, lib_source_id(name), lib_sources(name), ("-I", INCLUDE), force, verbose)
+    return _build(find(name).lib, lib_source_id(name), lib_sources(name), ("-I", INCLUDE), force, verbose)
 
 
 # The loss library.  It alone takes ``extra`` compiler flags (tuning knobs), which its source id then covers.
@@ -133,7 +133,7 @@ def build(force=False, verbose=True, extra=()):
 
 
 # Every other row, under its own names.
-for _row in TABLE[1:] + LATER:
+for _row in ROWS[1:]:
     globals().update({
         f"{_row.name.upper()}_CSRC": _row.csrc,
         f"{_row.name.upper()}_LIB": _row.lib,
@@ -188,7 +188,7 @@ def _build(lib, want, srcs, extra, force, verbose):
 
 
 if __name__ == "__main__":
-    for _row in TABLE + LATER:
+    for _row in ROWS:
         build_lib(_row.name, force="--force" in sys.argv)
-    for _row in TABLE + LATER:
+    for _row in ROWS:
         print(_row.lib)

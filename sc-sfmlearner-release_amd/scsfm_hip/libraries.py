@@ -4,8 +4,9 @@ __graft_entry__.build() reports them and tests/hostsim/library.py compiles them 
 A row holds what cannot be derived: the short name ("" for the loss library), the ABI version its header states, the
 tag build() reports it under and one line on what it computes.  The source directory, the header, the shared object and
 the symbol prefix follow from the short name.  ``TABLE`` is the sixteen rows whose number and order tests pin; a library
-added since goes into ``LATER``, and ``BY_NAME`` and ``SUMMARY`` cover both.  Imports nothing but os, so that
-scsfm_hip._lib can read it on import.
+added since goes into ``LATER``, and ``BY_NAME`` covers both; their number and ``BY_NAME``'s keys are pinned as well, so
+rows added after those go into ``NEWER``.  ``ROWS`` is every row, ``find(name)`` looks one up among all of them and
+``SUMMARY`` lists them all.  Imports nothing but os, so that scsfm_hip._lib can read it on import.
 """
 from __future__ import annotations
 
@@ -66,6 +67,20 @@ LATER = (
                                    "--freeze-bn)"),
 )
 BY_NAME = {row.name: row for row in TABLE + LATER}
+# Rows added after LATER and the keys of BY_NAME were fixed in their turn.  build() reports these ahead of LATER's, in a
+# wording of their own: "[<tag>] <path>: <n> entry points resolved (ABI <abi>)".
+NEWER = (
+    Library("opt", 1, "opt:build", "Adam over every parameter tensor in one launch (train.py --optimizer hip)"),
+)
+ROWS = TABLE + LATER + NEWER
+_FIND = {row.name: row for row in ROWS}
+
+
+def find(name):
+    """The row of the short name ``name``, among all rows."""
+    return _FIND[name]
+
+
 # one line per library, for the docstrings of build.py and _lib.py
 SUMMARY = "\n".join(f"    {os.path.basename(row.lib):22s} {os.path.basename(row.csrc) + '/':14s} "
-                    f"include/{os.path.basename(row.header):16s} {row.what}" for row in TABLE + LATER)
+                    f"include/{os.path.basename(row.header):16s} {row.what}" for row in ROWS)

@@ -23,6 +23,11 @@ Differences from the reference, all forced by the platform or by the scale-out d
   * `--shard-validation` (extension): every rank validates the batches it owns (scsfm_hip.validation.owner), each
     batch's result stays in a table on the device and the pass is reduced once at its end; without it rank 0 validates
     alone, as the reference's single process does.
+  * `--optimizer hip` (extension): Adam over all parameter tensors in one launch of libscsfm_opt.so with flat moments
+    (scsfm_hip/optim.py) instead of `torch.optim.Adam`; the default stays `torch`.
+  * `--save-state` / `--resume PATH` (extensions): after every epoch rank 0 also writes `train_state.pth.tar` -- the
+    optimiser's state, the counters, the best error, the logs' lengths and the random generators
+    (scsfm_hip/training_state.py) -- and `--resume` continues the run in its directory from its last completed epoch.
 """
 import argparse
 import contextlib
@@ -47,6 +52,8 @@ except ImportError:
 from scsfm_hip import config as hip_config
 from scsfm_hip import dist as hip_dist
 from scsfm_hip import encoder_frozen as hip_encoder_frozen
+from scsfm_hip import optim as hip_optim
+from scsfm_hip import training_state as hip_training_state
 from scsfm_hip import validation as hip_validation
 from scsfm_hip import validation_log as hip_validation_log
 from utils import save_checkpoint
@@ -114,6 +121,16 @@ parser.add_argument('--freeze-bn', default='off', choices=['off', 'stats', 'all'
                          'weights it was given for the whole run and never updates them (gamma and beta keep training); '
                          'all = gamma and beta are held too; off = the reference\'s batch statistics.  Needs weights for '
                          'both nets (--pretrained-disp / --pretrained-pose, or --with-pretrain 1)')
+parser.add_argument('--optimizer', default='torch', choices=['torch', 'hip'],
+                    help='torch = torch.optim.Adam; hip = the same update of all parameter tensors in one launch of a HIP '
+                         'kernel, the moments in two flat buffers (scsfm_hip/optim.py)')
+parser.add_argument('--save-state', action='store_true',
+                    help='after every epoch also write <save_path>/train_state.pth.tar: the optimizer state, the epoch, '
+                         'n_iter, the best error, the lengths of both logs and the random generators, for --resume')
+parser.add_argument('--resume', default=None, metavar='PATH',
+                    help='continue the run of this directory (or of its train_state.pth.tar) from its last completed epoch, '
+                         'in the same directory: both nets from its checkpoints, the rest from the state file.  Implies '
+                         '--save-state.  Exactly the straight run at world size 1 only')
 
 best_error = -1
 n_iter = 0
@@ -188,6 +205,13 @@ def build_datasets(args):
 def main():
     global best_error, n_iter, device
     args = parser.parse_args()
+    if args.resume:
+        # refused here, before any device or data set is touched; the state file itself is read on the host
+        why_not = hip_training_state.refusal(args)
+        if why_not:
+            parser.error(why_not)
+        args.save_state = True
+        args.with_pretrain = 0  # (both nets get the checkpoints' weights: nothing to initialise from)
     unsourced = nets_without_statistics(args)
     if unsourced:
         parser.error("--freeze-bn {} would hold the initial running statistics (mean 0, variance 1) of {}: give it weights "
@@ -221,7 +245,8 @@ def main():
         raise SystemExit("train.py needs a HIP device: the loss path has no CPU fallback")
 
     timestamp = datetime.datetime.now().strftime("%m-%d-%H:%M")
-    args.save_path = os.path.join('checkpoints', args.name, timestamp)
+    args.save_path = hip_training_state.locate(args.resume)[0] if args.resume else \
+        os.path.join('checkpoints', args.name, timestamp)
     if is_main:
         print('=> will save everything to {}'.format(args.save_path))
         os.makedirs(args.save_path, exist_ok=True)
@@ -274,6 +299,10 @@ def main():
         if is_main:
             print("=> using pre-trained weights for PoseResNet")
         pose_net.load_state_dict(torch.load(args.pretrained_pose, map_location=device)['state_dict'], strict=False)
+    resumed = hip_training_state.load(args.resume) if args.resume else None
+    if resumed is not None:
+        # every rank loads the same files: ranks other than 0 go on with rank 0's BatchNorm statistics
+        hip_training_state.load_nets(args.save_path, resumed['epoch'], disp_net, pose_net, device)
 
     if args.freeze_bn != 'off':
         # after the weights are in place; before DDP looks at requires_grad and before the optimizer's lists are formed
@@ -297,9 +326,15 @@ def main():
         print('=> setting adam solver')
     optim_params = [{'params': [p for p in disp_net.parameters() if p.requires_grad], 'lr': args.lr},
                     {'params': [p for p in pose_net.parameters() if p.requires_grad], 'lr': args.lr}]
-    optimizer = torch.optim.Adam(optim_params, betas=(args.momentum, args.beta), weight_decay=args.weight_decay)
+    optimizer = make_optimizer(args, optim_params)
 
-    if is_main:
+    start_epoch = 0
+    if resumed is not None:
+        start_epoch = restore_training_state(args, resumed, optimizer, rank, world)
+        if is_main:
+            print('=> resuming {} at epoch {} (n_iter {}, best_error {})'.format(args.save_path, start_epoch, n_iter,
+                                                                                 best_error))
+    elif is_main:
         with open(os.path.join(args.save_path, args.log_summary), 'w') as csvfile:
             csv.writer(csvfile, delimiter='\t').writerow(['train_loss', 'validation_loss'])
         with open(os.path.join(args.save_path, args.log_full), 'w') as csvfile:
@@ -307,7 +342,7 @@ def main():
 
     logger = TermLogger(n_epochs=args.epochs, train_size=min(len(train_loader), args.epoch_size), valid_size=len(val_loader))
     logger.epoch_bar.start()
-    for epoch in range(args.epochs):
+    for epoch in range(start_epoch, args.epochs):
         logger.epoch_bar.update(epoch)
         if train_sampler is not None:
             train_sampler.set_epoch(epoch)
@@ -337,6 +372,8 @@ def main():
                             {'epoch': epoch + 1, 'state_dict': p_net.state_dict()}, is_best)
             with open(os.path.join(args.save_path, args.log_summary), 'a') as csvfile:
                 csv.writer(csvfile, delimiter='\t').writerow([train_loss, decisive_error])
+            if args.save_state:  # (after the checkpoints and the summary row it counts)
+                hip_training_state.save(capture_training_state(args, epoch + 1, optimizer), args.save_path)
         if world > 1:
             torch.distributed.barrier()
     logger.epoch_bar.finish()
@@ -344,11 +381,31 @@ def main():
         torch.distributed.destroy_process_group()
 
 
+def make_optimizer(args, optim_params):
+    """Adam over the two groups (train.py:176-180 of the reference), from torch or in one launch of libscsfm_opt.so."""
+    adam = hip_optim.Adam if getattr(args, 'optimizer', 'torch') == 'hip' else torch.optim.Adam
+    return adam(optim_params, betas=(args.momentum, args.beta), weight_decay=args.weight_decay)
+
+
+def capture_training_state(args, next_epoch, optimizer):
+    """What --save-state writes after an epoch (scsfm_hip/training_state.py), of this module's counters."""
+    return hip_training_state.capture(args, next_epoch, n_iter, best_error, optimizer, device)
+
+
+def restore_training_state(args, state, optimizer, rank=0, world=1, generators=True):
+    """The optimizer's state, the lengths of the two logs, the generators and this module's counters from a saved state
+    -> the epoch to start at.  The nets are loaded before the optimizer is formed (training_state.load_nets)."""
+    global n_iter, best_error
+    epoch, n_iter, best_error = hip_training_state.restore(state, args, optimizer, device, rank, world, generators)
+    return epoch
+
+
 def nets_without_statistics(args):
-    """--freeze-bn holds the running statistics a net starts with, so each net needs a source of them: its own checkpoint
-    or the ImageNet weights.  -> [(the net's name, the flag that would give it weights)] for those that have none."""
-    if args.freeze_bn == 'off' or args.with_pretrain:
-        return []
+    """--freeze-bn holds the running statistics a net starts with, so each net needs a source of them: its own checkpoint,
+    the ImageNet weights or, with --resume, the run's checkpoints.  -> [(the net's name, the flag that would give it
+    weights)] for those that have none."""
+    if args.freeze_bn == 'off' or args.with_pretrain or getattr(args, 'resume', None):
+        return []  # (--resume: both nets get the run's checkpoints)
     return [(name, flag) for name, flag, path in (("DispResNet", "--pretrained-disp", args.pretrained_disp),
                                                    ("PoseResNet", "--pretrained-pose", args.pretrained_pose)) if not path]
 
