@@ -19,8 +19,15 @@ class PoseDecoder(nn.Module):
             nn.Conv2d(256, 6 * num_frames_to_predict_for, 1)])
         self.relu = nn.ReLU()
 
+    def _squeeze(self, x):
+        """net[0](x); on a HIP device its backward comes from scsfm_hip.conv1x1 where that applies"""
+        if x.is_cuda:
+            from scsfm_hip import conv1x1
+            return conv1x1.conv(self.net[0], x)
+        return self.net[0](x)
+
     def forward(self, input_features):
-        out = torch.cat([self.relu(self.net[0](f[-1])) for f in input_features], 1)
+        out = torch.cat([self.relu(self._squeeze(f[-1])) for f in input_features], 1)
         out = self.relu(self.net[1](out))
         out = self.relu(self.net[2](out))
         out = self.net[3](out)

@@ -85,9 +85,28 @@ def _bn_act(x, bn, act, identity=None):
     return out if act is None else act(out)
 
 
+_conv1x1_ops = None
+
+
+def _PW():
+    """scsfm_hip.conv1x1, imported on first use (a CPU-only run never loads it)"""
+    global _conv1x1_ops
+    if _conv1x1_ops is None:
+        from scsfm_hip import conv1x1
+        _conv1x1_ops = conv1x1
+    return _conv1x1_ops
+
+
 def _downsample(ds, x):
-    """the down-sample branch nn.Sequential(conv, bn)"""
-    return _bn_act(ds[0](x), ds[1], None)
+    """the down-sample branch nn.Sequential(conv, bn); the 1x1 convolution keeps its forward and takes its backward
+    from scsfm_hip.conv1x1 where that applies (CUDA fp32 contiguous NCHW with grad mode on, a routed shape) and the
+    blocks run the project's own glue: a BatchNorm in training mode, or one that scsfm_hip.encoder_frozen.freeze holds
+    (SCSFM_FROZEN_TORCH=1 sends a frozen net down the ATen chain whole, this convolution's backward included); a module
+    that is merely in eval mode keeps the plain call"""
+    conv, bn = ds[0], ds[1]
+    hip = x.is_cuda and (bn.training or (_EF().is_frozen(bn) and _EF().enabled()))
+    y = _PW().conv(conv, x) if hip else conv(x)
+    return _bn_act(y, bn, None)
 
 
 def _conv3x3(cin, cout, stride=1):

@@ -151,3 +151,22 @@ def decoder_dgrad():
 def set_decoder_dgrad(on):
     global _decoder_dgrad
     _decoder_dgrad = None if on is None else bool(on)
+
+
+_conv1x1_bwd = None
+
+
+def conv1x1_bwd():
+    """Do the encoders' 1x1 down-sample convolutions and the pose decoder's squeeze take their weight gradient, and the
+    stride-2 ones their input gradient, from libscsfm_pw.so (scsfm_hip.conv1x1.conv1x1) instead of MIOpen's backward
+    paths?  Default on; SCSFM_CONV1X1_BWD=0 (read once) or set_conv1x1_bwd(False) restore the plain module calls."""
+    global _conv1x1_bwd
+    if _conv1x1_bwd is None:
+        import os
+        _conv1x1_bwd = os.environ.get("SCSFM_CONV1X1_BWD", "1") != "0"
+    return _conv1x1_bwd
+
+
+def set_conv1x1_bwd(on):
+    global _conv1x1_bwd
+    _conv1x1_bwd = None if on is None else bool(on)

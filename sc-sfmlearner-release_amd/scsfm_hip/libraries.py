@@ -5,8 +5,8 @@ A row holds what cannot be derived: the short name ("" for the loss library), th
 tag build() reports it under and one line on what it computes.  The source directory, the header, the shared object and
 the symbol prefix follow from the short name.  ``TABLE`` is the sixteen rows whose number and order tests pin; a library
 added since goes into ``LATER``, and ``BY_NAME`` covers both; their number and ``BY_NAME``'s keys are pinned as well, so
-rows added after those go into ``NEWER``.  ``ROWS`` is every row, ``find(name)`` looks one up among all of them and
-``SUMMARY`` lists them all.  Imports nothing but os, so that scsfm_hip._lib can read it on import.
+rows added after those go into ``NEWER``.  ``ROWS`` is those three together, pinned in its turn, so rows added since stand
+in ``NEWEST``; ``EVERY`` is every row, ``find(name)`` looks one up among all of them and ``SUMMARY`` lists them all.  Imports nothing but os, so that scsfm_hip._lib can read it on import.
 """
 from __future__ import annotations
 
@@ -73,7 +73,13 @@ NEWER = (
     Library("opt", 1, "opt:build", "Adam over every parameter tensor in one launch (train.py --optimizer hip)"),
 )
 ROWS = TABLE + LATER + NEWER
-_FIND = {row.name: row for row in ROWS}
+# Rows added after ROWS was fixed as the sum of those three.  build() reports these directly behind NEWER's, in NEWER's
+# wording.
+NEWEST = (
+    Library("pw", 1, "pw:build", "the weight and stride-2 data gradients of the encoders' 1x1 down-sample convolutions"),
+)
+EVERY = ROWS + NEWEST
+_FIND = {row.name: row for row in EVERY}
 
 
 def find(name):
@@ -83,4 +89,4 @@ def find(name):
 
 # one line per library, for the docstrings of build.py and _lib.py
 SUMMARY = "\n".join(f"    {os.path.basename(row.lib):22s} {os.path.basename(row.csrc) + '/':14s} "
-                    f"include/{os.path.basename(row.header):16s} {row.what}" for row in ROWS)
+                    f"include/{os.path.basename(row.header):16s} {row.what}" for row in EVERY)

@@ -22,7 +22,12 @@ head), as the launches it used to be (direction `tail`: the head's sigmoid backw
 gradient of the 16 -> 1 convolution, the pad / ELU backward with its bias sum) and as libscsfm_dgrad.so's one pass
 (`tail_hip`); its bytes are what the one pass has to move (the padded tensor, the gradient it stores, three planes).
 `--tail-only` launches these two stretches alone, `--dgrad-only` these and the data gradients (`bwd`, `bwd_hip`) of the
-problems libscsfm_dgrad.so covers."""
+problems libscsfm_dgrad.so covers.
+
+`--pw-only` launches, for the 1x1 convolutions scsfm_hip.conv1x1 covers (the encoders' down-sample branches and the pose
+decoder's squeeze) and nothing else, MIOpen's weight gradient beside libscsfm_pw.so's two launches (`wrw`, `wrw_hip`) and,
+for stride 2, MIOpen's data gradient beside the library's one (`bwd`, `bwd_hip`).  The report's last column is the rate
+at which a call moves its operands' bytes, against the copy rate."""
 import argparse
 import json
 import os
@@ -119,14 +124,19 @@ def tail_calls(torch):
     return problem, {"tail": parts, "tail_hip": lambda: DG.tail_bwd(q, y, g_out, w, 10.0)}
 
 
-def run(iters, out, tail_only=False, dgrad_only=False):
+def run(iters, out, tail_only=False, dgrad_only=False, pw_only=False):
     import torch
 
     from bench import MIOPEN_SOLVERS_NEVER_CHOSEN
     for k in MIOPEN_SOLVERS_NEVER_CHOSEN:  # (the search space of bench.py's runs)
         os.environ.setdefault(k, "0")
-    from scsfm_hip import conv_wrw as CW
+    from scsfm_hip import conv_wrw as CW, conv1x1 as PW
     problems = [] if tail_only else collect()
+    pointwise = lambda p: (p["w"][2:] == (1, 1) and p["padding"] == (0, 0) and p["dilation"] == (1, 1)  # noqa: E731
+                           and p["groups"] == 1 and p["stride"][0] == p["stride"][1]
+                           and PW.covers(p["w"][1], p["w"][0], p["stride"][0]))
+    if pw_only:
+        problems = [p for p in problems if pointwise(p)]
     covered = lambda p: (p["w"][2:] == (3, 3) and p["stride"] == (1, 1) and p["padding"] == (0, 0)  # noqa: E731
                          and p["groups"] == 1 and CW.dgrad_covers(p["w"][1], p["w"][0]))
     if dgrad_only:
@@ -161,17 +171,25 @@ def run(iters, out, tail_only=False, dgrad_only=False):
             calls["wrw_hip"] = lambda: CW.weight_grad(x, gy)
         if covered(p):
             calls["bwd_hip"] = lambda: CW.data_grad(gy, w)
+        if pointwise(p):
+            s = p["stride"][0]
+            calls["wrw_hip"] = lambda: PW.weight_grad(x, gy, s)
+            if PW.dgrad_covers(p["w"][1], p["w"][0], s):
+                calls["bwd_hip"] = lambda: PW.data_grad(gy, w, p["x"][2], p["x"][3])
         if dgrad_only:
             calls = {d: c for d, c in calls.items() if d in ("bwd", "bwd_hip")}
+        if pw_only:
+            calls = {d: c for d, c in calls.items() if d != "fwd" and (d != "bwd" or "bwd_hip" in calls)}
         for d in DIRECTIONS:
             if d in calls:
                 stretch(pi, d, calls[d])
         del x, w, gy
         torch.cuda.empty_cache()
-    tail, calls = tail_calls(torch)
-    problems.append(tail)
-    for d, call in calls.items():
-        stretch(len(problems) - 1, d, call)
+    if not pw_only:
+        tail, calls = tail_calls(torch)
+        problems.append(tail)
+        for d, call in calls.items():
+            stretch(len(problems) - 1, d, call)
     with open(out, "w") as f:
         json.dump({"problems": problems, "segments": segments}, f, indent=1)
     print(f"launched {len(segments)} stretches of {iters} calls over {len(problems)} problems; wrote {out}")
@@ -235,7 +253,8 @@ def report(db, seg_file):
         label = layers[0] + (f" (+{len(layers) - 1})" if len(layers) > 1 else "")
         print(f"{p['per_step']:3d} {seg['direction']:8s} {total:8.1f} us  spread {spread}  {flop / 1e9:6.2f} GFLOP "
               f"{moved / 1e6:7.1f} MB  floors {f_mat:6.1f} {f_byte:6.1f} us  x{total / max(f_mat, f_byte):5.2f}  "
-              f"{ws[1]}->{ws[0]} {ws[2]}x{ws[3]} s{p['stride'][0]} p{p['padding'][0]} @ {ys[2]}x{ys[3]}  {label}")
+              f"{ws[1]}->{ws[0]} {ws[2]}x{ws[3]} s{p['stride'][0]} p{p['padding'][0]} @ {ys[2]}x{ys[3]}  {label}  "
+              f"{moved / total / 1e3:5.0f} GB/s = {100 * moved / total / 1e3 / (COPY_RATE / 1e9):3.0f}% of the copy rate")
         print("        " + "; ".join(parts))
 
 
@@ -248,5 +267,8 @@ if __name__ == "__main__":
     ap.add_argument("--tail-only", action="store_true", help="launch the two stretches of the decoder's tail alone")
     ap.add_argument("--dgrad-only", action="store_true",
                     help="launch the tail and the data gradients of the problems libscsfm_dgrad.so covers alone")
+    ap.add_argument("--pw-only", action="store_true",
+                    help="launch the weight and data gradients of the 1x1 convolutions libscsfm_pw.so covers alone")
     args = ap.parse_args()
-    report(args.report, args.segments) if args.report else run(args.iters, args.out, args.tail_only, args.dgrad_only)
+    report(args.report, args.segments) if args.report else run(args.iters, args.out, args.tail_only, args.dgrad_only,
+                                                               args.pw_only)
