@@ -1,0 +1,162 @@
+"""Dense voxel reconstruction of a sequence from the estimated depth and poses: PoseResNet gives the trajectory,
+DispResNet the depth of every frame, and both are fused into a truncated signed distance volume whose surface points are
+written as a coloured point cloud.  The reference shows this use of scale-consistent predictions and ships no program for
+it; this one follows test_vo.py's and run_inference.py's flags.
+
+    python reconstruct.py --pretrained-dispnet checkpoints/dispnet_model_best.pth.tar \
+        --pretrained-posenet checkpoints/exp_pose_model_best.pth.tar --resnet-layers 18 \
+        --dataset-dir kitti_odom_test/sequences/09/image_2 --intrinsics kitti_256/09_2/cam.txt \
+        --max-depth 10 --voxel-size 0.05 --output-dir results/recon/
+
+Pass one runs the pose net over the consecutive pairs of frames and folds the pose vectors on the device
+(scsfm_hip.odometry.chain_poses), as test_vo.py does.  The volume is the box of the camera centres grown by --max-depth on
+every side.  Pass two runs the disparity net in batches and integrates every batch on the device
+(scsfm_hip.fusion.Volume, libscsfm_fuse.so): no prediction is copied to the host.  <output-dir>/reconstruction.ply holds
+the surface points (binary little-endian: float x y z, uchar red green blue), <output-dir>/poses.txt the trajectory in
+test_vo.py's format (12 numbers a frame, '%1.8e', the first one the identity).
+
+Units: the predictions have the nets' own scale -- consistent along the sequence, which is what lets the frames be fused,
+but not metric.  --max-depth, --voxel-size and --trunc are in those units (the nets' depth is 1 / disparity, between 0.1
+and 100).  The frames are decoded on the host, resized on the device as run_inference.py resizes them, and --intrinsics
+(a 3 x 3 text file like the prepared data's cam.txt, for the frames as they are stored) is rescaled with them.
+"""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+import run_inference
+
+parser = argparse.ArgumentParser(description='Dense voxel reconstruction from the estimated depth and poses (TSDF fusion '
+                                 'on the device). All lengths are in the units of the nets\' predictions, which are '
+                                 'consistent along a sequence but not metric.',
+                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+parser.add_argument("--pretrained-dispnet", required=True, type=str, help="pretrained DispResNet path")
+parser.add_argument("--pretrained-posenet", required=True, type=str, help="pretrained PoseResNet path")
+parser.add_argument('--resnet-layers', type=int, default=18, choices=[18, 50], help='depth network architecture.')
+parser.add_argument("--dataset-dir", required=True, type=str, help="a folder of frames, taken in sorted order")
+parser.add_argument("--intrinsics", required=True, type=str,
+                    help="3x3 text file (as cam.txt) of the frames as stored; rescaled when they are resized")
+parser.add_argument("--img-height", default=256, type=int, help="Image height")
+parser.add_argument("--img-width", default=832, type=int, help="Image width")
+parser.add_argument("--no-resize", action='store_true', help="no resizing is done")
+parser.add_argument("--img-exts", default=['png', 'jpg', 'bmp'], nargs='*', type=str, help="images extensions to glob")
+parser.add_argument("--rotation-mode", default='euler', choices=['euler', 'quat'], type=str)
+parser.add_argument("--batch-size", default=8, type=int,
+                    help="frames per forward pass; a batch is integrated in launches of --frames-per-launch, so keep it "
+                         "at least that large")
+parser.add_argument("--max-depth", default=10.0, type=float,
+                    help="predicted depths beyond this are not fused, and the box is grown by it (the nets' units)")
+parser.add_argument("--voxel-size", default=None, type=float, help="edge of a voxel (the nets' units)")
+parser.add_argument("--resolution", default=None, type=int,
+                    help="voxels along the longest side of the box, instead of --voxel-size (default 256)")
+parser.add_argument("--trunc", default=None, type=float,
+                    help="truncation distance; default 3 voxels (scsfm_hip.fusion.TRUNC_VOXELS)")
+parser.add_argument("--min-weight", default=2.0, type=float,
+                    help="a surface point needs both voxels of its edge seen at least this often")
+parser.add_argument("--frames-per-launch", default=None, type=int,
+                    help="frames one launch of the integration carries (default scsfm_hip.fusion.FRAMES_PER_LAUNCH)")
+parser.add_argument("--every", default=1, type=int, metavar="N", help="fuse every N-th frame (all frames give the poses)")
+parser.add_argument("--output-dir", default='output', type=str, help="Output directory")
+
+
+def scaled_intrinsics(K, stored_hw, used_hw):
+    """cam.txt's matrix for frames resized from stored_hw to used_hw: the first row scales with the width, the second
+    with the height (as the data loaders and data/prepare_train_data.py scale it)"""
+    K = np.array(K, np.float64).reshape(3, 3)
+    K[0] *= used_hw[1] / stored_hw[1]
+    K[1] *= used_hw[0] / stored_hw[0]
+    return K.astype(np.float32)
+
+
+def frames(files, args, device, bs):
+    """(first index, normalised float32 [n, 3, H, W] on the device, stored (H, W)) per batch of at most bs frames"""
+    from scsfm_hip import visualise
+    args = argparse.Namespace(**{**vars(args), "batch_size": bs})
+    k = 0
+    for batch in run_inference.batches(files, args):
+        yield k, visualise.normalise_u8(run_inference.stage(batch, args, device)), batch[0][1].shape[:2]
+        k += len(batch)
+
+
+@torch.no_grad()
+def main(argv=None, on_poses=None, on_batch=None):
+    """``on_poses(vec)`` and ``on_batch(disp, imgs, c2w, K)`` -- for the tests -- are handed the pose vectors
+    [n - 1, 6] and every fused batch's tensors, all on the device."""
+    args = parser.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("reconstruct.py needs a HIP device")
+    if args.voxel_size is not None and args.resolution is not None:
+        raise SystemExit("give either --voxel-size or --resolution")
+    if args.every < 1 or args.batch_size < 1:
+        raise SystemExit("--every and --batch-size must be at least 1")
+    device = torch.device("cuda")
+    import models
+    from scsfm_hip import fusion
+    from scsfm_hip.odometry import chain_poses
+
+    disp_net = models.DispResNet(args.resnet_layers, False).to(device)
+    disp_net.load_state_dict(torch.load(args.pretrained_dispnet, map_location=device)['state_dict'])
+    disp_net.eval()
+    pose_net = models.PoseResNet(18, False).to(device)
+    pose_net.load_state_dict(torch.load(args.pretrained_posenet, map_location=device)['state_dict'], strict=False)
+    pose_net.eval()
+
+    args.dataset_list = None
+    files = run_inference.list_files(args)
+    print('{} files to reconstruct from'.format(len(files)))
+    if len(files) < 2:
+        raise SystemExit("reconstruct.py needs at least two frames")
+    os.makedirs(args.output_dir, exist_ok=True)
+
+    # pass one: the trajectory
+    vecs, last, sizes = [], None, set()
+    for _, imgs, stored in frames(files, args, device, args.batch_size):
+        sizes.add((stored, tuple(imgs.shape[-2:])))
+        seq = imgs if last is None else torch.cat([last, imgs])
+        if len(seq) > 1:
+            vecs.append(pose_net(seq[:-1], seq[1:]))
+        last = imgs[-1:]
+    if len(sizes) != 1:
+        raise SystemExit("the frames of a reconstruction must all have one size")
+    (stored_hw, used_hw), = sizes
+    vec = torch.cat(vecs).float()
+    if on_poses is not None:
+        on_poses(vec)
+    c2w = chain_poses(vec, args.rotation_mode).contiguous()  # float64 [n, 3, 4], on the device
+    np.savetxt(os.path.join(args.output_dir, "poses.txt"), c2w.reshape(-1, 12).cpu().numpy(), delimiter=' ', fmt='%1.8e')
+    K = scaled_intrinsics(np.genfromtxt(args.intrinsics), stored_hw, used_hw)
+
+    # the box
+    lo, hi = fusion.camera_box(c2w, args.max_depth)
+    voxel = args.voxel_size if args.voxel_size is not None else float((hi - lo).max()) / (args.resolution or 256)
+    origin, dims = fusion.bounds_from_cameras(c2w, args.max_depth, voxel)
+    nvox = dims[0] * dims[1] * dims[2]
+    print('volume: {} x {} x {} voxels of {:.6g}, {:.1f} MB, corner ({:.4g}, {:.4g}, {:.4g})'.format(
+        *dims, voxel, 20 * nvox / 1e6, *origin))
+    if nvox > fusion.MAX_VOXELS:
+        raise SystemExit("a volume of {} voxels is above the limit of 2^29: choose a larger --voxel-size (or a smaller "
+                         "--resolution or --max-depth)".format(nvox))
+    vol = fusion.Volume(dims, origin, voxel, args.trunc, device=device,
+                        frames_per_launch=args.frames_per_launch or fusion.FRAMES_PER_LAUNCH)
+    K_dev = torch.from_numpy(K).to(device)
+
+    # pass two: the depth of every N-th frame, fused batch by batch on the device
+    chosen = list(range(0, len(files), args.every))
+    for k, imgs, _ in frames([files[i] for i in chosen], args, device, args.batch_size):
+        disp = disp_net(imgs)
+        idx = torch.tensor(chosen[k:k + len(imgs)], device=device)
+        batch = (disp.contiguous(), imgs, c2w[idx].contiguous(), K_dev)
+        if on_batch is not None:
+            on_batch(*batch)
+        vol.integrate(*batch, is_disp=True, max_depth=args.max_depth)
+    xyz, rgb = vol.extract(args.min_weight)
+    path = os.path.join(args.output_dir, "reconstruction.ply")
+    fusion.write_ply(path, xyz, rgb)
+    print('{} surface points from {} frames -> {}'.format(len(xyz), len(chosen), path))
+    return vol
+
+
+if __name__ == '__main__':
+    main()

@@ -6,7 +6,9 @@ tag build() reports it under and one line on what it computes.  The source direc
 the symbol prefix follow from the short name.  ``TABLE`` is the sixteen rows whose number and order tests pin; a library
 added since goes into ``LATER``, and ``BY_NAME`` covers both; their number and ``BY_NAME``'s keys are pinned as well, so
 rows added after those go into ``NEWER``.  ``ROWS`` is those three together, pinned in its turn, so rows added since stand
-in ``NEWEST``; ``EVERY`` is every row, ``find(name)`` looks one up among all of them and ``SUMMARY`` lists them all.  Imports nothing but os, so that scsfm_hip._lib can read it on import.
+in ``NEWEST``; ``EVERY``, pinned as ``ROWS + NEWEST``, is those four, so rows added since stand in ``NEXT``; ``ALL`` is
+every row, ``find(name)`` looks one up among all of them and ``SUMMARY`` lists them all.  Imports nothing but os, so
+that scsfm_hip._lib can read it on import.
 """
 from __future__ import annotations
 
@@ -79,7 +81,14 @@ NEWEST = (
     Library("pw", 1, "pw:build", "the weight and stride-2 data gradients of the encoders' 1x1 down-sample convolutions"),
 )
 EVERY = ROWS + NEWEST
-_FIND = {row.name: row for row in EVERY}
+# Rows added after EVERY was fixed as the sum of ROWS and NEWEST.  build() reports these directly behind LATER's lines, in
+# NEWER's wording (the lines that end in "entry points resolved" are counted).
+NEXT = (
+    Library("fuse", 1, "fuse:build", "the TSDF fusion of predicted depth and poses and the surface points of "
+                                     "reconstruct.py"),
+)
+ALL = EVERY + NEXT
+_FIND = {row.name: row for row in ALL}
 
 
 def find(name):
@@ -89,4 +98,4 @@ def find(name):
 
 # one line per library, for the docstrings of build.py and _lib.py
 SUMMARY = "\n".join(f"    {os.path.basename(row.lib):22s} {os.path.basename(row.csrc) + '/':14s} "
-                    f"include/{os.path.basename(row.header):16s} {row.what}" for row in EVERY)
+                    f"include/{os.path.basename(row.header):16s} {row.what}" for row in ALL)
