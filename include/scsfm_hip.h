@@ -191,8 +191,17 @@ typedef struct scsfm_pair_desc {
   void* smooth_out;  /* with smooth_ws: 1 element (store) = this frame's loss */
   void* smooth_total; /* read from d[0] only, may be NULL: 1 element (store) = the sum of smooth_out over the descriptors
                          that carry a smooth_ws, in descriptor order = compute_smooth_loss (loss_functions.py:154-159)
-                         when each frame of the step is the target of exactly one of them */
+                         when each frame of the step is the target of exactly one of them.  REQUIRES d[0].total: the
+                         workgroup that finishes the pair totals forms this sum too (smooth_total without total: argument
+                         error, nothing is launched) */
 } scsfm_pair_desc;
+
+/* w_photo / w_geom of scsfm_pairs_fwd, scsfm_pairs_fwd_step and scsfm_pair_fwd_spec: the speculation is decided on the
+ * weights ROUNDED TO THE ELEMENT TYPE (float / double), which is also how the objective of scsfm_pairs_fwd_step uses
+ * them.  The backward lets the speculative results stand when g_geom * T(w_photo) == g_photo * T(w_geom) exactly; with
+ * the upstream gradients of scsfm_step_weights, g = T(T(w) * g_loss), that holds for every g_loss that is a power of two
+ * and for every pair of dyadic weights, and otherwise not in general -- the backward then runs its own two passes and
+ * returns the same gradients.  A w_photo that rounds to zero counts as zero (no speculation). */
 
 int scsfm_pairs_fwd_f32(int n, const scsfm_pair_desc* d, int B, int H, int W, const float* intrinsics,
                         unsigned flags, double w_photo, double w_geom, void* stream);

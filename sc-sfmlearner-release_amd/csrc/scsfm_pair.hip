@@ -1363,7 +1363,14 @@ static int pairs_fwd(int n, const scsfm_pair_desc* d, int B, int H, int W, const
   if (n < 0 || (n > 0 && !d) || B <= 0 || H < 2 || W < 2 || !dims_ok<T>(B, H, W) || !K) return SCSFM_ERR_ARG;
   for (int i = 0; i < n; ++i)
     if (!desc_inputs_ok(d[i], H, W) || !d[i].out) return SCSFM_ERR_ARG;
+  // the last arriver of the finalize launch forms both totals together: the smooth one has nowhere to go without the other
+  if (n > 0 && d[0].smooth_total && !d[0].total) return SCSFM_ERR_ARG;
   hipStream_t stream = (hipStream_t)stream_;
+  // The speculation is decided on the weights ROUNDED TO T: the upstream gradients the backward compares them with
+  // (spec_valid) are T values -- T(w) * g_loss from scsfm_step_weights, or autograd's product of T tensors -- and the products
+  // of its check are exact only between such values.  (-c 0.3 in fp32: fl32(0.3) * 1.0 != 1.0 * 0.3 failed the check on
+  // every step.)  The loss value does not move: st.w1 .. w3 below are T(w) anyway.
+  w_photo = double(T(w_photo)); w_geom = double(T(w_geom));
   // maximal runs of descriptors with the same mode (speculative or plain), at most kMaxPairs each
   const double* hint = n > 0 ? (const double*)d[0].hint : nullptr;
   const bool may_spec = w_photo != 0.0 || hint != nullptr;

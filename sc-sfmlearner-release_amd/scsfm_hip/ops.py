@@ -220,8 +220,11 @@ class StepLoss(torch.autograd.Function):
     them: five scalar kernels forward, three backward, and one elementwise addition per depth map (the smooth
     gradient is accumulated into the buffers the pair backward just stored).  The speculation hint is the
     weights themselves -- this node knows them, unlike PhotoGeometryLoss, which learns the ratio from the upstream
-    gradients it sees and therefore keeps it on the device (config.hint_tensor) -- so the speculation holds whatever
-    the upstream gradient of the loss is (the check is on the RATIO of the two terms' gradients)."""
+    gradients it sees and therefore keeps it on the device (config.hint_tensor).  With T the tensors' dtype and the
+    weights rounded to it, the speculation stands when T(w_geom * g_loss) * w_photo == T(w_photo * g_loss) * w_geom --
+    always for an upstream gradient g_loss that is a power of two (1, a loss scaler's scales), always for dyadic weights
+    (the defaults 1 / 0.5), otherwise not in general -- and when it does not, the backward's own passes give the same
+    gradients."""
 
     @staticmethod
     def forward(ctx, flags, n_ref, n_scales, w_photo, w_smooth, w_geom, tgt_img, K, *rest):

@@ -944,13 +944,12 @@ def test_other_loss_weights_converge_to_the_speculative_path(LF, dev):
     fl = capi.make_flags(1, 1, 1, "zeros")
     hint_dev = torch.tensor([1.0, 0.5], dtype=torch.float64, device=dev)
     gp, gg = torch.full((1,), w1, device=dev), torch.full((1,), w3, device=dev)
-    ws_bytes, scratch_bytes, _ = capi._sizes(lib, 12, 256, 832)
+    from _spec_rule import sums_of
     held = []
     for _ in range(3):
         _, _, _, ws = capi.photo_geometry_fwd(lib, fl, tgt, K, refs, tds, rds, ps, pis, hint=(1.0, 0.5), hint_dev=hint_dev)
         capi.photo_geometry_bwd(lib, fl, tgt, K, refs, tds, rds, ps, pis, ws, gp, gg, hint_dev=hint_dev)
-        stride = ws_bytes + scratch_bytes
-        held.append([float(ws[j * stride + 256 * 12 + 64:j * stride + 256 * 12 + 72].view(torch.float64)) for j in range(4)])
+        held.append([float(sums_of(lib, ws, j, 12, 256, 832)[8]) for j in range(4)])
     assert held == [[0.0] * 4, [1.0] * 4, [1.0] * 4], held
     config.set_weight_hint(1.0, 0.5)  # (the package default again, on the host and in the device copy)
 
@@ -1165,3 +1164,74 @@ def test_iid_pose_gradients_as_row_statistics_over_seeds(LF, dev):
         assert x <= IID_ROW_FACTOR * y + POSE_RTOL, st
     for x, y in zip(st["hip/row"][:2], st["ref/row"][:2]):
         assert x <= IID_ROW_FACTOR * y + POSE_RTOL, st
+
+
+# ------------------------------------------------------------------------------------------------
+# 9. the one-node step (compute_total_loss) at other weights than 1 / 0.1 / 0.5: the hardware twins of
+#    tests/test_hostsim_smooth_ride.py (the same kernels with other scalar arguments; 4 x 72 x 100, one reference)
+# ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def step_case(dev):
+    import _spec_rule as R
+    from scsfm_hip import _lib
+    return R, _lib.get(), R.inputs(torch.float32, dev)
+
+
+@pytest.mark.parametrize("g_loss", [1.0, 65536.0])
+@pytest.mark.parametrize("w", [(1.0, 0.1, 0.5), (0.7, 0.1, 0.3)], ids=lambda w: "-".join(map(str, w)))
+def test_speculation_stands_for_the_weights_a_run_can_have(step_case, w, g_loss):
+    """StepLoss's library calls: the forward stores the weights rounded to fp32, the speculation of both pair-directions
+    stands after the backward, the gradients equal the fp64 oracle's."""
+    R, lib, x = step_case
+    R.check_step(lib, x, w, g_loss, True, stored=(float(np.float32(w[0])), float(np.float32(w[2]))))
+
+
+@pytest.mark.parametrize("g_loss", [1 / 3, 3.7, 1 / 12], ids=["third", "3.7", "twelfth"])
+@pytest.mark.parametrize("w", [(1.0, 0.1, 0.5), (1.0, 0.1, 0.3), (0.7, 0.1, 0.3)], ids=lambda w: "-".join(map(str, w)))
+def test_speculation_stands_exactly_when_the_restated_rule_says_so(step_case, w, g_loss):
+    """Upstream gradients that are no powers of two: sums[8] after the backward is what _spec_rule.spec_holds says of the
+    stored pair, and the gradients equal the fp64 oracle's on either route."""
+    R, lib, x = step_case
+    R.check_step(lib, x, w, g_loss, None, stored=(float(np.float32(w[0])), float(np.float32(w[2]))))
+
+
+@pytest.mark.parametrize("w", [(0.7, 0.1, 0.3), (1.0, 0.1, 0.0)], ids=lambda w: "-".join(map(str, w)))
+def test_single_node_step_at_other_weights(LF, dev, step_case, monkeypatch, w):
+    """compute_total_loss through autograd: values and gradients against the fp64 oracle on the CPU, and the workspace that
+    reaches the backward still holds a standing speculation afterwards.  The time of loss.backward() is reported
+    (informative: the host's enqueue of autograd's own kernels hides most of it)."""
+    from scsfm_hip import capi
+    R, lib, x = step_case
+    B, H, W, n_ref, _ = R.CASE
+    ti, K, ris, tds, rds, ps, pis = x
+    seen = []
+    real_bwd = capi.photo_geometry_bwd
+
+    def recording(*a, **k):
+        seen.append(a[9])  # ws
+        return real_bwd(*a, **k)
+
+    monkeypatch.setattr(capi, "photo_geometry_bwd", recording)
+    vals, _ = R.oracle_terms()
+    for c in (1.0, 0.125):
+        lf = lambda t: t.clone().requires_grad_(True)
+        td, rd, pp, pi = [lf(t) for t in tds], [[lf(r[0])] for r in rds], [lf(p) for p in ps], [lf(p) for p in pis]
+        loss, photo, smooth, geom = LF.compute_total_loss(ti, ris, K, td, rd, pp, pi, 1, 1, 1, 1, "zeros", *w)
+        del seen[:]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        (c * loss).backward()
+        e1.record()
+        torch.cuda.synchronize()
+        report(f"one-node step w={w} c={c}: loss.backward() {e0.elapsed_time(e1):.3f} ms (4 x 72 x 100, one reference)")
+        assert len(seen) == 1
+        for j in range(2 * n_ref):
+            s = R.sums_of(lib, seen[0], j, B, H, W).cpu()
+            assert float(s[5]) != 0.0 and float(s[6]) != 0.0
+            assert float(s[8]) == 1.0, (w, c, j, s[8:11].tolist())
+        got = [float(v) for v in (photo, smooth, geom)]
+        assert all(abs(a - b) <= 1e-5 for a, b in zip(got, vals)), (got, vals)
+        assert abs(float(loss.detach()) - (w[0] * vals[0] + w[1] * vals[1] + w[2] * vals[2])) <= 1e-5 * (w[0] + w[1] + w[2])
+        R.judge_gradients([t.grad for t in td + [r[0] for r in rd] + pp + pi], R.oracle_gradients(w, c), torch.float32,
+                          what=f"w={w} c={c}")

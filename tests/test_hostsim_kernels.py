@@ -813,12 +813,7 @@ def test_smooth_gradient_rides_along_in_the_combining_pass(lib, H, W, dtype, hin
         assert _rel(x - y, z) < (1e-9 if dtype == torch.float64 else 2e-3)
 
 
-def _sums_of(lib, ws, j, B, H, W):
-    """double[16] of pair j's workspace (csrc/scsfm_common.h: PairWs -- the B constants slots of 256 bytes come first)."""
-    ws_bytes, scratch_bytes, _ = capi._sizes(lib, B, H, W)
-    stride = ws_bytes + scratch_bytes
-    off = j * stride + 256 * B
-    return ws[off:off + 128].view(torch.float64)
+from _spec_rule import sums_of as _sums_of  # noqa: E402  (double[16] of pair j's workspace; shared with the hardware tests)
 
 
 def test_the_device_side_hint_follows_the_upstream_gradients(lib):

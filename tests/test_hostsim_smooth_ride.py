@@ -2,6 +2,7 @@
 :50-92 as train.py:262-268 calls them) in the CPU simulation of the product sources: against the stand-alone smooth forward
 (the edge planes and the per-image records it leaves must be THE SAME -- the backward entry points are shared), against the
 fp64 oracle, and with the pair losses of the same call untouched."""
+import numpy as np
 import pytest
 import torch
 
@@ -94,6 +95,39 @@ def test_descriptors_the_fold_cannot_serve_are_rejected(lib):
     d[0].gbuf = ws.data_ptr() + ws_bytes
     assert call(0.0) == -1            # a gbuf, but nothing to speculate on
     assert call(1.0) == 0             # the speculative forward carries it
+
+
+def test_smooth_total_without_total_is_rejected(lib):
+    """scsfm_pair_desc::smooth_total is formed by the workgroup that finishes d[0].total: set without it, the value was
+    never written and the call returned 0.  Now SCSFM_ERR_ARG from all four entry points, and nothing is launched: the
+    output buffers keep their bits."""
+    import ctypes as ct
+    B, H, W = 2, 32, 64
+    for dtype, sfx in ((torch.float32, "f32"), (torch.float64, "f64")):
+        ti, K, ris, tds, rds, ps, pis = _inputs(B, H, W, 1, dtype, "smooth")
+        ws_bytes, scratch_bytes, sw_bytes = capi._sizes(lib, B, H, W)
+        ws = torch.full((ws_bytes + scratch_bytes,), 0xA5, dtype=torch.uint8)
+        sws = torch.full((sw_bytes,), 0xA5, dtype=torch.uint8)
+        out, souts, step_out = (torch.full((n,), -77.25, dtype=dtype) for n in (10, 2, 4))
+        d = (capi.PairDesc * 1)()
+        d[0].tgt_img, d[0].ref_img, d[0].tgt_depth, d[0].ref_depth, d[0].pose = ti.data_ptr(), ris[0].data_ptr(), \
+            tds[0].data_ptr(), rds[0][0].data_ptr(), ps[0].data_ptr()
+        d[0].ws, d[0].gbuf, d[0].out, d[0].smooth_ws = ws.data_ptr(), ws.data_ptr() + ws_bytes, out.data_ptr(), sws.data_ptr()
+        d[0].smooth_out, d[0].smooth_total = souts.data_ptr(), souts.data_ptr() + souts.element_size()
+        fwd = lambda: lib._fn[f"scsfm_pairs_fwd_{sfx}"](1, ct.addressof(d), B, H, W, K.data_ptr(), 7, 1.0, 0.5, 0)
+        step = lambda: lib._fn[f"scsfm_pairs_fwd_step_{sfx}"](1, ct.addressof(d), B, H, W, K.data_ptr(), 7, 1.0, 0.1, 0.5,
+                                                              step_out.data_ptr(), 0)
+        assert d[0].total is None
+        assert fwd() == -1 and step() == -1
+        untouched = lambda: bool((ws == 0xA5).all()) and bool((sws == 0xA5).all()) and \
+            all(bool((t == -77.25).all()) for t in (out, souts, step_out))
+        assert untouched()
+        d[0].smooth_total = None  # without either total the plain call is served ...
+        assert fwd() == 0 and float(souts[1]) == -77.25 and float(souts[0]) != -77.25
+        d[0].smooth_total, d[0].total = souts.data_ptr() + souts.element_size(), out.data_ptr() + 8 * out.element_size()
+        assert fwd() == 0 and step() == 0  # ... and with both
+        assert float(souts[1]) == float(souts[0]) and float(step_out[2]) == float(souts[0])
+        assert abs(float(step_out[0]) - (float(out[8]) + 0.1 * float(souts[0]) + 0.5 * float(out[9]))) <= 1e-6
 
 
 # ---- the host mirror: the reference's two calls (train.py:262-266) with the smooth loss found waiting -----------------
@@ -227,3 +261,112 @@ def test_each_loss_can_be_differentiated_on_its_own(on_sim):
             # in the device-side hint, so the second run's forward speculates on them and its backward is the scaled add
             # of fixed-point planes where the first ran the fallback passes: 1e-6-sized differences)
             assert float((a - b).abs().max()) <= 2e-5 * scale + (0 if scale else 1e-30), which
+
+
+# ---- the one-node step at other weights than 1 / 0.1 / 0.5: does its speculation stand, and are the gradients right? ---
+import _spec_rule as R  # noqa: E402
+
+STEP_WEIGHTS = [(1.0, 0.1, 0.5), (0.7, 0.1, 0.3), (1.0, 0.1, 0.3), (0.85, 0.05, 0.15), (1.0, 0.1, 0.1)]  # -p / -s / -c of a run
+RULE_WEIGHTS = [(1.0, 0.1, 0.5), (1.0, 0.1, 0.3), (0.7, 0.1, 0.3)]
+RULE_GRADIENTS = [1 / 3, 3.7, 1 / 12]
+
+
+@pytest.fixture(scope="module")
+def step_case():
+    return {dt: R.inputs(dt) for dt in (torch.float32, torch.float64)}
+
+
+@pytest.mark.parametrize("g_loss", [1.0, 0.125, 65536.0])
+@pytest.mark.parametrize("w", STEP_WEIGHTS, ids=lambda w: "-".join(map(str, w)))
+def test_speculation_stands_for_the_weights_a_run_can_have(lib, step_case, w, g_loss):
+    """StepLoss's library calls in fp32 with upstream gradients that are powers of two (1, a loss scaler's scales): the
+    forward stores the weights ROUNDED TO fp32, every pair-direction's speculation stands after the backward (sums[8] ==
+    1), and the gradients equal the fp64 oracle's.  (With the unrounded doubles in sums[9..10] every triple but the
+    first one ran the fallback passes on every step.)"""
+    stored = (float(np.float32(w[0])), float(np.float32(w[2])))
+    assert R.spec_holds(w[0], w[2], g_loss, torch.float32, stored)
+    R.check_step(lib, step_case[torch.float32], w, g_loss, True, stored=stored)
+
+
+def test_the_rule_table_has_both_outcomes():
+    for dt, T in ((torch.float32, np.float32), (torch.float64, np.float64)):
+        got = {R.spec_holds(w[0], w[2], g, dt, (float(T(w[0])), float(T(w[2])))) for w in RULE_WEIGHTS for g in RULE_GRADIENTS}
+        assert got == {True, False}, dt
+        assert all(R.spec_holds(1.0, 0.5, g, dt, (1.0, 0.5)) for g in RULE_GRADIENTS)  # dyadic weights: always
+    assert not any(R.spec_holds(0.7, 0.3, g, torch.float32, (float(np.float32(0.7)), float(np.float32(0.3)))) for g in RULE_GRADIENTS)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("g_loss", RULE_GRADIENTS, ids=["third", "3.7", "twelfth"])
+@pytest.mark.parametrize("w", RULE_WEIGHTS, ids=lambda w: "-".join(map(str, w)))
+def test_speculation_stands_exactly_when_the_restated_rule_says_so(lib, step_case, w, g_loss, dtype):
+    """Upstream gradients that are no powers of two: T(w_geom g) w_photo == T(w_photo g) w_geom decides (always true for the
+    dyadic 1 / 0.5; false for 0.7 / 0.3 in fp32 at each of these gradients), sums[8] after the backward says what
+    _spec_rule.spec_holds says of the pair the forward stored -- the weights rounded to the element type -- and on either
+    route the gradients equal the fp64 oracle's."""
+    T = np.float32 if dtype == torch.float32 else np.float64
+    R.check_step(lib, step_case[dtype], w, g_loss, None, stored=(float(T(w[0])), float(T(w[2]))))
+
+
+AUTOGRAD_WEIGHTS = [(0.7, 0.1, 0.3), (1.0, 0.0, 0.5), (1.0, 0.1, 0.0), (0.0, 0.1, 0.5), (0.0, 0.0, 0.5)]
+
+
+@pytest.mark.parametrize("w", AUTOGRAD_WEIGHTS, ids=lambda w: "-".join(map(str, w)))
+def test_single_node_step_at_other_and_zero_weights(on_sim, lib, monkeypatch, w):
+    """compute_total_loss against the three reference-style calls plus the weighted sum, values and every gradient, with
+    loss.backward() and (0.125 * loss).backward().  -c 0: r_hint = 0;
+    -s 0: the smooth gradient rides as zeros; -p 0: no hint, the plain forward and ONE stand-alone smooth forward.  Where
+    the step speculates, the workspace that reaches the backward still holds a standing speculation afterwards."""
+    from scsfm_hip import config
+    import loss_functions as LF
+    B, H, W, n_ref, seed = R.CASE
+    rides = w[0] != 0
+    seen = []
+    real_bwd = capi.photo_geometry_bwd
+
+    def recording(*a, **k):
+        seen.append(a[9])  # ws
+        return real_bwd(*a, **k)
+
+    z = lambda t: torch.zeros_like(t) if t.grad is None else t.grad.clone()
+
+    def reference(c):
+        ti, ris, K, td, rd, ps, pis = _leaves(B, H, W, n_ref, seed)
+        photo, geom = LF.compute_photo_and_geometry_loss(ti, ris, K, td, rd, ps, pis, 1, 1, 1, 1, "zeros")
+        smooth = LF.compute_smooth_loss(td, ti, rd, ris)
+        loss = w[0] * photo + w[1] * smooth + w[2] * geom
+        (c * loss).backward()
+        return [float(v.detach()) for v in (loss, photo, smooth, geom)], [z(td[0])] + [z(r[0]) for r in rd] + [z(p) for p in ps + pis]
+
+    def step(c):
+        ti, ris, K, td, rd, ps, pis = _leaves(B, H, W, n_ref, seed)
+        n0 = on_sim["smooth_fwd"]
+        loss, photo, smooth, geom = LF.compute_total_loss(ti, ris, K, td, rd, ps, pis, 1, 1, 1, 1, "zeros", *w)
+        # which route ran: the speculative forward carries the smooth loss unless -p 0 switches the speculation off
+        assert on_sim["smooth_fwd"] - n0 == (0 if rides else 1), w
+        del seen[:]
+        (c * loss).backward()
+        assert len(seen) == 1
+        if rides:
+            for j in range(2 * n_ref):
+                s = R.sums_of(lib, seen[0], j, B, H, W)
+                assert float(s[5]) != 0.0 and float(s[6]) != 0.0
+                assert float(s[8]) == 1.0, (w, c, j, s[8:11].tolist())
+        return [float(v.detach()) for v in (loss, photo, smooth, geom)], [z(td[0])] + [z(r[0]) for r in rd] + [z(p) for p in ps + pis]
+
+    config.set_smooth_rides_along(True)
+    monkeypatch.setattr(capi, "photo_geometry_bwd", recording)
+    for c in (1.0, 0.125):
+        # the reference-style calls speculate on the same weights (a user of the reference's loop with other -p / -c says
+        # config.set_weight_hint(p, c), INTEGRATION.md): both sides then take the same route to the gradients, which is
+        # what the 1e-6 below presumes (across routes the fixed-point planes differ by more: the oracle judges those, above)
+        config.set_weight_hint(w[0], w[2])
+        try:
+            v0, g0 = reference(c)
+        finally:
+            config.set_weight_hint(1.0, 0.5)  # the package default
+        v1, g1 = step(c)
+        for a, b in zip(v1, v0):
+            assert abs(a - b) <= 1e-6 * abs(b), (w, c, v1, v0)
+        for k, (a, b) in enumerate(zip(g1, g0)):
+            assert float((a - b).abs().max()) <= 1e-6 * float(b.abs().max()), (w, c, k)

@@ -11,7 +11,7 @@ import pytest
 
 from scsfm_hip import _lib, build
 
-LOSS_ID = "dc1122dba412f24a"
+LOSS_ID = "a4885409350e4bef"  # (since the speculation weights are rounded to the element type; dc1122dba412f24a before)
 NETS_ID = "5e9e8a56c343fa9b"
 EVAL_ID = "fcc94374d9bcd5ba"
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
