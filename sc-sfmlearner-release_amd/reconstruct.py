@@ -13,7 +13,9 @@ Pass one runs the pose net over the consecutive pairs of frames and folds the po
 every side.  Pass two runs the disparity net in batches and integrates every batch on the device
 (scsfm_hip.fusion.Volume, libscsfm_fuse.so): no prediction is copied to the host.  <output-dir>/reconstruction.ply holds
 the surface points (binary little-endian: float x y z, uchar red green blue), <output-dir>/poses.txt the trajectory in
-test_vo.py's format (12 numbers a frame, '%1.8e', the first one the identity).
+test_vo.py's format (12 numbers a frame, '%1.8e', the first one the identity).  With --mesh, <output-dir>/mesh.ply also
+holds the surface as an indexed triangle mesh (scsfm_hip.meshing, libscsfm_mesh.so: marching tetrahedra on the voxel
+grid; the same vertex format, then faces of three int indices); the other two files are the same bytes with and without it.
 
 Units: the predictions have the nets' own scale -- consistent along the sequence, which is what lets the frames be fused,
 but not metric.  --max-depth, --voxel-size and --trunc are in those units (the nets' depth is 1 / disparity, between 0.1
@@ -58,6 +60,9 @@ parser.add_argument("--min-weight", default=2.0, type=float,
 parser.add_argument("--frames-per-launch", default=None, type=int,
                     help="frames one launch of the integration carries (default scsfm_hip.fusion.FRAMES_PER_LAUNCH)")
 parser.add_argument("--every", default=1, type=int, metavar="N", help="fuse every N-th frame (all frames give the poses)")
+parser.add_argument("--mesh", action='store_true',
+                    help="also write <output-dir>/mesh.ply: the surface as an indexed triangle mesh (marching tetrahedra "
+                         "on the device, scsfm_hip.meshing)")
 parser.add_argument("--output-dir", default='output', type=str, help="Output directory")
 
 
@@ -155,6 +160,12 @@ def main(argv=None, on_poses=None, on_batch=None):
     path = os.path.join(args.output_dir, "reconstruction.ply")
     fusion.write_ply(path, xyz, rgb)
     print('{} surface points from {} frames -> {}'.format(len(xyz), len(chosen), path))
+    if args.mesh:
+        from scsfm_hip import meshing
+        path = os.path.join(args.output_dir, "mesh.ply")
+        xyz, rgb, tri = vol.extract_mesh(args.min_weight)
+        meshing.write_ply_mesh(path, xyz, rgb, tri)
+        print('{} vertices, {} triangles -> {}'.format(len(xyz), len(tri), path))
     return vol
 
 

@@ -154,6 +154,12 @@ class Volume:
                        _stream(self.device))
         return xyz, rgb
 
+    def extract_mesh(self, min_weight=1.0):
+        """-> (xyz float32 [V, 3], rgb uint8 [V, 3], tri int32 [T, 3]) on the device: the surface as an indexed triangle
+        mesh (scsfm_hip.meshing.extract_mesh, libscsfm_mesh.so)."""
+        from . import meshing
+        return meshing.extract_mesh(self, min_weight)
+
 
 def camera_box(c2w, max_depth):
     """The box of the camera centres grown by ``max_depth`` on every side -> (lo, hi), two float64 arrays of 3.
