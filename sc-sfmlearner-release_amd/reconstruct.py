@@ -17,6 +17,14 @@ test_vo.py's format (12 numbers a frame, '%1.8e', the first one the identity).  
 holds the surface as an indexed triangle mesh (scsfm_hip.meshing, libscsfm_mesh.so: marching tetrahedra on the voxel
 grid; the same vertex format, then faces of three int indices); the other two files are the same bytes with and without it.
 
+With --render a third pass brings the fused model back into the image domain (scsfm_hip.raycast, libscsfm_cast.so: one ray
+per pixel marched through the volume): the pose of every fused frame is cast, in batches of --batch-size views, into
+<output-dir>/fused_depth.npy (float32 [n, H, W]: the units and layout of 1 / disp, as run_inference.py's predictions.npy,
+0 where no surface is seen) and <output-dir>/render/<frame name>_shade.png (lit from the camera) and _colour.png.  The
+pass runs the disparity net again, batch by batch, and prints how far each frame's own prediction is from the model all
+frames agreed on.  --render-poses FILE casts the poses of a text file in poses.txt's format instead (novel views, or
+another run's trajectory); its pictures are named by index.  The older files are the same bytes with and without it.
+
 Units: the predictions have the nets' own scale -- consistent along the sequence, which is what lets the frames be fused,
 but not metric.  --max-depth, --voxel-size and --trunc are in those units (the nets' depth is 1 / disparity, between 0.1
 and 100).  The frames are decoded on the host, resized on the device as run_inference.py resizes them, and --intrinsics
@@ -63,6 +71,15 @@ parser.add_argument("--every", default=1, type=int, metavar="N", help="fuse ever
 parser.add_argument("--mesh", action='store_true',
                     help="also write <output-dir>/mesh.ply: the surface as an indexed triangle mesh (marching tetrahedra "
                          "on the device, scsfm_hip.meshing)")
+parser.add_argument("--render", action='store_true',
+                    help="also cast the pose of every fused frame through the volume: <output-dir>/fused_depth.npy and "
+                         "<output-dir>/render/*_shade.png, *_colour.png (scsfm_hip.raycast)")
+parser.add_argument("--render-poses", default=None, type=str, metavar="FILE",
+                    help="cast these poses instead (poses.txt's format: 12 numbers a line, camera to world); implies "
+                         "--render, names the pictures by index")
+parser.add_argument("--render-step", default=None, type=float,
+                    help="distance between two samples of a ray, as a depth (the nets' units); default the voxel size")
+parser.add_argument("--render-near", default=0.0, type=float, help="depth of a ray's first sample (the nets' units)")
 parser.add_argument("--output-dir", default='output', type=str, help="Output directory")
 
 
@@ -85,11 +102,79 @@ def frames(files, args, device, bs):
         k += len(batch)
 
 
+def read_poses(path):
+    """--render-poses' file -> float64 [n, 3, 4]: n >= 1 lines of 12 finite numbers, camera to world"""
+    try:
+        with open(path) as f:
+            rows = [[float(v) for v in line.split()] for line in f if line.strip() and not line.lstrip().startswith("#")]
+    except (OSError, ValueError) as e:
+        raise SystemExit("--render-poses {}: {}".format(path, e))
+    if not rows or any(len(r) != 12 for r in rows):
+        raise SystemExit("--render-poses {}: every line must hold 12 numbers (a 3 x 4 camera-to-world matrix, as "
+                         "poses.txt), and there must be at least one".format(path))
+    poses = np.array(rows, np.float64)
+    if not np.isfinite(poses).all():
+        raise SystemExit("--render-poses {}: a pose that is not finite".format(path))
+    return poses.reshape(-1, 3, 4)
+
+
+def render(args, vol, disp_net, views, K_dev, hw, device, names, files=None, on_render=None):
+    """The third pass: casts ``views`` (float64 [n, 3, 4] on the device) in batches and writes fused_depth.npy and the
+    pictures.  With ``files`` (the fused frames, one per view) the disparity net runs again batch by batch and the
+    agreement of its depth with the fused one is summed on the device, in float64, and read back once."""
+    from PIL import Image
+
+    from scsfm_hip import raycast
+    out_dir = os.path.join(args.output_dir, "render")
+    os.makedirs(out_dir, exist_ok=True)
+    mask = raycast.brick_mask(vol, args.min_weight)
+    far = args.max_depth + vol.trunc
+    sums = torch.zeros(3, dtype=torch.float64, device=device)  # pixels with a hit, pixels compared, sum of the ratios
+    preds = frames(files, args, device, args.batch_size) if files is not None else None
+    depths = []
+    for k in range(0, len(views), args.batch_size):
+        batch = views[k:k + args.batch_size].contiguous()
+        got = vol.raycast(batch, K_dev, hw, args.render_near, far, step=args.render_step, min_weight=args.min_weight,
+                          mask=mask)
+        if on_render is not None:
+            on_render(got, batch)
+        hit = got.depth > 0
+        sums[0] += hit.sum()
+        if preds is not None:
+            k0, imgs, _ = next(preds)
+            assert k0 == k and len(imgs) == len(batch)
+            pred = 1.0 / disp_net(imgs)[:, 0]
+            both = hit & (pred <= args.max_depth)
+            ratio = (pred.double() - got.depth.double()).abs() / got.depth.double()
+            sums[1] += both.sum()
+            sums[2] += torch.where(both, ratio, torch.zeros_like(ratio)).sum()
+        depths.append(got.depth.cpu().numpy())
+        rgb, shade = got.rgb.cpu().numpy(), got.shade.cpu().numpy()
+        for j in range(len(batch)):
+            Image.fromarray(shade[j]).save(os.path.join(out_dir, names[k + j] + "_shade.png"))
+            Image.fromarray(rgb[j]).save(os.path.join(out_dir, names[k + j] + "_colour.png"))
+    path = os.path.join(args.output_dir, "fused_depth.npy")
+    np.save(path, np.concatenate(depths))
+    n_hit, n_both, total = sums.tolist()
+    share = n_hit / (len(views) * hw[0] * hw[1])
+    if preds is None:
+        print('rendered {} views -> {}: {:.9g} of the pixels with a hit'.format(len(views), path, share))
+    else:
+        print('rendered {} views -> {}: {:.9g} of the pixels with a hit; mean |pred - fused| / fused {:.9g} over {} '
+              'pixels'.format(len(views), path, share, total / n_both if n_both else float("nan"), int(n_both)))
+
+
 @torch.no_grad()
-def main(argv=None, on_poses=None, on_batch=None):
-    """``on_poses(vec)`` and ``on_batch(disp, imgs, c2w, K)`` -- for the tests -- are handed the pose vectors
-    [n - 1, 6] and every fused batch's tensors, all on the device."""
+def main(argv=None, on_poses=None, on_batch=None, on_render=None):
+    """``on_poses(vec)``, ``on_batch(disp, imgs, c2w, K)`` and ``on_render(result, views)`` -- for the tests -- are
+    handed the pose vectors [n - 1, 6], every fused batch's tensors, and every rendered batch's scsfm_hip.raycast.Cast with
+    its poses [b, 3, 4], all on the device."""
     args = parser.parse_args(argv)
+    novel = read_poses(args.render_poses) if args.render_poses is not None else None
+    if args.render_step is not None and not (args.render_step > 0 and np.isfinite(args.render_step)):
+        raise SystemExit("--render-step must be positive")
+    if not (args.render_near >= 0 and np.isfinite(args.render_near)):
+        raise SystemExit("--render-near must not be negative")
     if not torch.cuda.is_available():
         raise SystemExit("reconstruct.py needs a HIP device")
     if args.voxel_size is not None and args.resolution is not None:
@@ -166,6 +251,14 @@ def main(argv=None, on_poses=None, on_batch=None):
         xyz, rgb, tri = vol.extract_mesh(args.min_weight)
         meshing.write_ply_mesh(path, xyz, rgb, tri)
         print('{} vertices, {} triangles -> {}'.format(len(xyz), len(tri), path))
+    if novel is not None:
+        render(args, vol, disp_net, torch.from_numpy(novel).to(device), K_dev, used_hw, device,
+               ['{:06d}'.format(i) for i in range(len(novel))], on_render=on_render)
+    elif args.render:
+        fused = [files[i] for i in chosen]
+        names = [os.path.splitext(os.path.basename(str(f)))[0] for f in fused]
+        render(args, vol, disp_net, c2w[torch.tensor(chosen, device=device)], K_dev, used_hw, device, names, files=fused,
+               on_render=on_render)
     return vol
 
 

@@ -160,6 +160,12 @@ class Volume:
         from . import meshing
         return meshing.extract_mesh(self, min_weight)
 
+    def raycast(self, c2w, K, hw, near, far, **kwargs):
+        """-> raycast.Cast(depth float32 [V, H, W], normal float32 [V, 3, H, W], rgb uint8 [V, H, W, 3], shade uint8
+        [V, H, W]) on the device: the volume seen from the poses ``c2w`` (scsfm_hip.raycast.cast, libscsfm_cast.so)."""
+        from . import raycast
+        return raycast.cast(self, c2w, K, hw, near, far, **kwargs)
+
 
 def camera_box(c2w, max_depth):
     """The box of the camera centres grown by ``max_depth`` on every side -> (lo, hi), two float64 arrays of 3.

@@ -7,9 +7,11 @@ the symbol prefix follow from the short name.  ``TABLE`` is the sixteen rows who
 added since goes into ``LATER``, and ``BY_NAME`` covers both; their number and ``BY_NAME``'s keys are pinned as well, so
 rows added after those go into ``NEWER``.  ``ROWS`` is those three together, pinned in its turn, so rows added since stand
 in ``NEWEST``; ``EVERY``, pinned as ``ROWS + NEWEST``, is those four, so rows added since stand in ``NEXT``; ``ALL``, pinned
-as ``EVERY + NEXT`` with twenty rows, is those five, so rows added since stand in ``BEYOND``; ``LIBRARIES`` is every
-row, ``find(name)`` looks one up among all of them and ``SUMMARY`` lists them all.  Imports nothing but os, so that
-scsfm_hip._lib can read it on import.
+as ``EVERY + NEXT`` with twenty rows, is those five, so rows added since stand in ``BEYOND``; ``LIBRARIES``, pinned
+as ``ALL + BEYOND`` with twenty-one rows, is those six, and ``SUMMARY`` lists them, one line each, pinned too; so rows added
+since stand in ``FURTHER``.  ``CATALOGUE`` is every row: the loops that build, load and name the libraries run over it,
+and ``find(name)`` looks a row up among all of them.  Imports nothing but os, so that scsfm_hip._lib can read it on
+import.
 """
 from __future__ import annotations
 
@@ -96,7 +98,14 @@ BEYOND = (
                                      "--mesh)"),
 )
 LIBRARIES = ALL + BEYOND
-_FIND = {row.name: row for row in LIBRARIES}
+# Rows added after LIBRARIES was fixed as the sum of ALL and BEYOND, and SUMMARY as its lines.  build() reports these ahead
+# of every other line, in a wording of their own: "[<tag>] <path>: ABI <abi>, <n> symbols of include/<header>".
+FURTHER = (
+    Library("cast", 1, "cast:build", "the ray cast of a fused volume from camera poses: depth, normals, colour and shaded "
+                                     "pictures (reconstruct.py --render)"),
+)
+CATALOGUE = LIBRARIES + FURTHER
+_FIND = {row.name: row for row in CATALOGUE}
 
 
 def find(name):
@@ -104,6 +113,7 @@ def find(name):
     return _FIND[name]
 
 
-# one line per library, for the docstrings of build.py and _lib.py
+# one line per library of LIBRARIES, for the docstrings of build.py and _lib.py (FURTHER's rows: libscsfm_cast.so, csrc_cast/,
+# include/scsfm_cast.h)
 SUMMARY = "\n".join(f"    {os.path.basename(row.lib):22s} {os.path.basename(row.csrc) + '/':14s} "
                     f"include/{os.path.basename(row.header):16s} {row.what}" for row in LIBRARIES)
