@@ -25,6 +25,14 @@ pass runs the disparity net again, batch by batch, and prints how far each frame
 frames agreed on.  --render-poses FILE casts the poses of a text file in poses.txt's format instead (novel views, or
 another run's trajectory); its pictures are named by index.  The older files are the same bytes with and without it.
 
+With --refine-poses pass two closes the loop, as KinectFusion does (scsfm_hip.tracking, libscsfm_track.so): the first fused
+frame is integrated at its chained pose; the others are taken in groups of --refine-group, each frame's guess is the pose
+net's relative motion applied to the refined pose of the last frame before the group, the group is aligned to the model
+fused so far by --refine-iterations of point-to-plane ICP against its ray cast, and integrated at the refined poses.  A
+frame that never finds enough pairs, or a well-conditioned system, keeps its guess.  poses.txt stays the chain;
+<output-dir>/poses_refined.txt has the same format (a frame that is not fused follows the refined frame before it by the
+chain's relative motion), and reconstruction.ply, mesh.ply and the casts of --render are of the refined model and poses.
+
 Units: the predictions have the nets' own scale -- consistent along the sequence, which is what lets the frames be fused,
 but not metric.  --max-depth, --voxel-size and --trunc are in those units (the nets' depth is 1 / disparity, between 0.1
 and 100).  The frames are decoded on the host, resized on the device as run_inference.py resizes them, and --intrinsics
@@ -80,6 +88,16 @@ parser.add_argument("--render-poses", default=None, type=str, metavar="FILE",
 parser.add_argument("--render-step", default=None, type=float,
                     help="distance between two samples of a ray, as a depth (the nets' units); default the voxel size")
 parser.add_argument("--render-near", default=0.0, type=float, help="depth of a ray's first sample (the nets' units)")
+parser.add_argument("--refine-poses", action='store_true',
+                    help="align every fused frame to the model fused so far before it is integrated (frame-to-model ICP, "
+                         "scsfm_hip.tracking); also writes <output-dir>/poses_refined.txt")
+parser.add_argument("--refine-iterations", default=10, type=int, metavar="N", help="ICP iterations per frame (1 .. 64)")
+parser.add_argument("--refine-group", default=1, type=int, metavar="G",
+                    help="frames aligned and integrated together: 1 is KinectFusion's loop; more trades the later "
+                         "frames' view of the earlier ones for fewer and fuller launches")
+parser.add_argument("--refine-max-dist", default=None, type=float, metavar="D",
+                    help="a frame's point and the model's point pair up to this distance (the nets' units); default "
+                         "the truncation distance")
 parser.add_argument("--output-dir", default='output', type=str, help="Output directory")
 
 
@@ -164,12 +182,87 @@ def render(args, vol, disp_net, views, K_dev, hw, device, names, files=None, on_
               'pixels'.format(len(views), path, share, total / n_both if n_both else float("nan"), int(n_both)))
 
 
+def relative_to(anchor_refined, anchor, poses):
+    """anchor_refined @ inverse(anchor) @ poses[i]: the chain's motion from the anchor frame to each of ``poses``
+    (float64 [n, 3, 4], rigid, camera to world) applied to the anchor's refined pose -> float64 [n, 3, 4].  In double, with
+    torch on the device; a rigid pose's inverse is (R^T, -R^T t)."""
+    Ra, ta = anchor[:, :3], anchor[:, 3]
+    Rr, tr = anchor_refined[:, :3], anchor_refined[:, 3]
+    R = Rr @ (Ra.T @ poses[:, :, :3])
+    t = (Rr @ (Ra.T @ (poses[:, :, 3] - ta).T)).T + tr
+    return torch.cat([R, t[:, :, None]], dim=2).contiguous()
+
+
+def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None, on_track=None):
+    """Pass two with --refine-poses (see the module's docstring) -> the refined poses of all frames, float64 [n, 3, 4] on
+    the device.  The figures of the printed line are summed on the device, in float64, and read back once."""
+    from scsfm_hip import tracking
+    refined = c2w.clone()
+    done = 0                                # chosen frames fused so far
+    sums = torch.zeros(6, dtype=torch.float64, device=device)  # rms first / last (sum, frames), pair share, kept
+
+    def fuse(disp, imgs, idx, poses):
+        batch = (disp, imgs, poses.contiguous(), K_dev)
+        if on_batch is not None:
+            on_batch(*batch)
+        vol.integrate(*batch, is_disp=True, max_depth=args.max_depth)
+        refined[idx] = poses
+
+    for first, group in ((True, 1), (False, args.refine_group)):
+        todo = chosen[:1] if first else chosen[1:]
+        if not todo:
+            continue
+        for k, imgs, _ in frames([files[i] for i in todo], args, device, group):
+            disp = disp_net(imgs).contiguous()
+            ids = todo[k:k + len(imgs)]
+            idx = torch.tensor(ids, device=device)
+            if first:
+                fuse(disp, imgs, idx, c2w[idx])
+                continue
+            anchor = chosen[done]               # the last frame before the group
+            guess = relative_to(refined[anchor], c2w[anchor], c2w[idx])
+            got = vol.track(disp, guess, K_dev, is_disp=True, max_depth=args.max_depth,
+                            iterations=args.refine_iterations, max_dist=args.refine_max_dist)
+            if on_track is not None:
+                on_track(ids, guess, got, disp)
+            kept = tracking.kept_guess(got.report)
+            fuse(disp, imgs, idx, torch.where(kept[:, None, None], guess, got.c2w))
+            done += len(ids)
+            count, rr = got.report[:, :, 0], got.report[:, :, 1]
+            for j, it in ((0, 0), (2, -1)):
+                some = count[:, it] > 0
+                rms = torch.sqrt(rr[:, it] / torch.where(some, count[:, it], torch.ones_like(count[:, it])))
+                sums[j] += torch.where(some, rms, torch.zeros_like(rms)).sum()
+                sums[j + 1] += some.sum()
+            sums[4] += count[:, -1].sum() / (disp.shape[-2] * disp.shape[-1])
+            sums[5] += kept.sum()
+    # a frame that is not fused follows the refined frame before it
+    for a, b in zip(chosen, chosen[1:] + [len(c2w)]):
+        if b > a + 1:
+            refined[a + 1:b] = relative_to(refined[a], c2w[a], c2w[a + 1:b])
+    path = os.path.join(args.output_dir, "poses_refined.txt")
+    np.savetxt(path, refined.reshape(-1, 12).cpu().numpy(), delimiter=' ', fmt='%1.8e')
+    first_sum, first_n, last_sum, last_n, share, kept = sums.tolist()
+    n = len(chosen) - 1
+    print('refined {} poses -> {}: mean rms residual {:.12g} -> {:.12g}, mean pair share {:.12g}, {} frames kept their '
+          'guess'.format(n, path, first_sum / first_n if first_n else float("nan"),
+                         last_sum / last_n if last_n else float("nan"), share / n if n else float("nan"), int(kept)))
+    return refined
+
+
 @torch.no_grad()
-def main(argv=None, on_poses=None, on_batch=None, on_render=None):
-    """``on_poses(vec)``, ``on_batch(disp, imgs, c2w, K)`` and ``on_render(result, views)`` -- for the tests -- are
-    handed the pose vectors [n - 1, 6], every fused batch's tensors, and every rendered batch's scsfm_hip.raycast.Cast with
-    its poses [b, 3, 4], all on the device."""
+def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None):
+    """``on_poses(vec)``, ``on_batch(disp, imgs, c2w, K)``, ``on_render(result, views)`` and ``on_track(indices, guess,
+    track, disp)`` -- for the tests -- are handed the pose vectors [n - 1, 6], every fused batch's tensors, every rendered
+    batch's scsfm_hip.raycast.Cast with its poses [b, 3, 4], and every tracked group's frame indices, guessed poses
+    [g, 3, 4], scsfm_hip.tracking.Track and disparities, all on the device."""
     args = parser.parse_args(argv)
+    if not 1 <= args.refine_iterations <= 64:
+        raise SystemExit("--refine-iterations must be between 1 and 64")
+    if args.refine_group < 1:
+        raise SystemExit("--refine-group must be at least 1")
+    if args.refine_max_dist is not None and not (args.refine_max_dist > 0 and np.isfinite(args.refine_max_dist)):
+        raise SystemExit("--refine-max-dist must be positive")
     novel = read_poses(args.render_poses) if args.render_poses is not None else None
     if args.render_step is not None and not (args.render_step > 0 and np.isfinite(args.render_step)):
         raise SystemExit("--render-step must be positive")
@@ -234,7 +327,9 @@ def main(argv=None, on_poses=None, on_batch=None, on_render=None):
 
     # pass two: the depth of every N-th frame, fused batch by batch on the device
     chosen = list(range(0, len(files), args.every))
-    for k, imgs, _ in frames([files[i] for i in chosen], args, device, args.batch_size):
+    if args.refine_poses:
+        c2w = refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch, on_track)
+    for k, imgs, _ in () if args.refine_poses else frames([files[i] for i in chosen], args, device, args.batch_size):
         disp = disp_net(imgs)
         idx = torch.tensor(chosen[k:k + len(imgs)], device=device)
         batch = (disp.contiguous(), imgs, c2w[idx].contiguous(), K_dev)

@@ -21,7 +21,7 @@ import threading
 # hipErrorNoDevice.)
 import torch  # noqa: F401  (must precede ctypes.CDLL below)
 
-from .libraries import ALL, BY_NAME, CATALOGUE, EVERY, HERE, LATER, LIBRARIES, ROWS, SUMMARY, TABLE  # noqa: F401  (ALL, EVERY, HERE, LATER, LIBRARIES, ROWS: as before)
+from .libraries import ALL, BY_NAME, CATALOGUE, EVERY, HERE, LATER, LIBRARIES, REGISTRY, ROWS, SUMMARY, TABLE  # noqa: F401  (ALL, CATALOGUE, EVERY, HERE, LATER, LIBRARIES, ROWS: as before)
 
 __doc__ = (__doc__ or "") + SUMMARY + "\n"
 
@@ -140,7 +140,7 @@ def _getter(row):
 
 
 get = _getter(TABLE[0])
-for _row in CATALOGUE[1:]:
+for _row in REGISTRY[1:]:
     globals().update({
         f"{_row.name.upper()}_HEADER": _row.header,
         f"{_row.name.upper()}_LIB_PATH": _row.lib,

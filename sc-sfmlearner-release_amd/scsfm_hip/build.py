@@ -31,7 +31,7 @@ import subprocess
 import sys
 import tempfile
 
-from .libraries import ALL, BY_NAME, CATALOGUE, EVERY, HERE, INCLUDE, LATER, LIBRARIES, ROWS, SUMMARY, TABLE, find  # noqa: F401  (ALL, EVERY, LATER, LIBRARIES, ROWS: as before)
+from .libraries import ALL, BY_NAME, CATALOGUE, EVERY, HERE, INCLUDE, LATER, LIBRARIES, REGISTRY, ROWS, SUMMARY, TABLE, find  # noqa: F401  (ALL, CATALOGUE, EVERY, LATER, LIBRARIES, ROWS: as before)
 
 __doc__ = (__doc__ or "") + SUMMARY + "\n"
 
@@ -133,7 +133,7 @@ def build(force=False, verbose=True, extra=()):
 
 
 # Every other row, under its own names.
-for _row in CATALOGUE[1:]:
+for _row in REGISTRY[1:]:
     globals().update({
         f"{_row.name.upper()}_CSRC": _row.csrc,
         f"{_row.name.upper()}_LIB": _row.lib,
@@ -188,7 +188,7 @@ def _build(lib, want, srcs, extra, force, verbose):
 
 
 if __name__ == "__main__":
-    for _row in CATALOGUE:
+    for _row in REGISTRY:
         build_lib(_row.name, force="--force" in sys.argv)
-    for _row in CATALOGUE:
+    for _row in REGISTRY:
         print(_row.lib)

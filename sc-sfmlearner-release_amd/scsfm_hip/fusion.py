@@ -166,6 +166,13 @@ class Volume:
         from . import raycast
         return raycast.cast(self, c2w, K, hw, near, far, **kwargs)
 
+    def track(self, depth_or_disp, guess, K, **kwargs):
+        """-> tracking.Track(c2w float64 [V, 3, 4], report, model_depth, model_normal, state) on the device: the poses
+        ``guess`` of V frames refined against this volume by point-to-plane ICP (scsfm_hip.tracking.track,
+        libscsfm_track.so)."""
+        from . import tracking
+        return tracking.track(self, depth_or_disp, guess, K, **kwargs)
+
 
 def camera_box(c2w, max_depth):
     """The box of the camera centres grown by ``max_depth`` on every side -> (lo, hi), two float64 arrays of 3.

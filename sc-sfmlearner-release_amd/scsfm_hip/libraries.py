@@ -9,9 +9,12 @@ rows added after those go into ``NEWER``.  ``ROWS`` is those three together, pin
 in ``NEWEST``; ``EVERY``, pinned as ``ROWS + NEWEST``, is those four, so rows added since stand in ``NEXT``; ``ALL``, pinned
 as ``EVERY + NEXT`` with twenty rows, is those five, so rows added since stand in ``BEYOND``; ``LIBRARIES``, pinned
 as ``ALL + BEYOND`` with twenty-one rows, is those six, and ``SUMMARY`` lists them, one line each, pinned too; so rows added
-since stand in ``FURTHER``.  ``CATALOGUE`` is every row: the loops that build, load and name the libraries run over it,
-and ``find(name)`` looks a row up among all of them.  Imports nothing but os, so that scsfm_hip._lib can read it on
-import.
+since stand in ``FURTHER``.  ``CATALOGUE``, pinned as ``LIBRARIES + FURTHER`` with twenty-two rows, is those seven.
+
+``ADDED`` ends the ratchet: it is the open-ended tuple.  Every library added from libscsfm_track.so on is appended to
+it, and no test pins its length or its contents -- a test asserts that its own row is in it.  ``REGISTRY`` is
+``CATALOGUE + ADDED``, every row: the loops that build, load and name the libraries run over it, and ``find(name)`` looks
+a row up among all of them.  Imports nothing but os, so that scsfm_hip._lib can read it on import.
 """
 from __future__ import annotations
 
@@ -105,7 +108,14 @@ FURTHER = (
                                      "pictures (reconstruct.py --render)"),
 )
 CATALOGUE = LIBRARIES + FURTHER
-_FIND = {row.name: row for row in CATALOGUE}
+# Rows added after CATALOGUE was fixed as the sum of LIBRARIES and FURTHER.  The open-ended tuple: the next library is
+# appended here.  build() reports these ahead of FURTHER's lines, in FURTHER's wording.
+ADDED = (
+    Library("track", 1, "track:build", "the frame-to-model tracking of predicted depth against the ray-cast model by "
+                                       "point-to-plane ICP (reconstruct.py --refine-poses)"),
+)
+REGISTRY = CATALOGUE + ADDED
+_FIND = {row.name: row for row in REGISTRY}
 
 
 def find(name):
