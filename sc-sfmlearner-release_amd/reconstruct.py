@@ -33,6 +33,18 @@ frame that never finds enough pairs, or a well-conditioned system, keeps its gue
 <output-dir>/poses_refined.txt has the same format (a frame that is not fused follows the refined frame before it by the
 chain's relative motion), and reconstruction.ply, mesh.ply and the casts of --render are of the refined model and poses.
 
+With --consistency-weight every observation enters the volume with the depth consistency of its pixel as its weight
+(scsfm_hip.confidence, libscsfm_conf.so): pass two first runs the disparity net over all fused frames and keeps the
+disparities on the device, every frame is compared with its --consistency-radius neighbours on either side among the fused
+frames (with --every N they are N frames apart) at the chain's poses -- one minus the depth inconsistency of the training
+loss, |D_computed - D_projected| / (D_computed + D_projected), averaged over the neighbours or, with --consistency-reduce
+max, the best of them -- and the frames are then integrated from the stored disparities with that weight: a pixel below
+--consistency-floor, or with fewer than --consistency-min-views neighbours to compare with, is not fused at all.  With
+--refine-poses the weights are still those of the chain's poses (its relative poses do not depend on the refinement, and
+the frames ahead are not refined yet), and the alignment itself stays unweighted.  --output-confidence writes
+<output-dir>/confidence.npy (float32 [n, H, W]) and <output-dir>/confidence/<frame name>.png (8-bit grey).  Without
+--consistency-weight every file and printed line is what it was.
+
 Units: the predictions have the nets' own scale -- consistent along the sequence, which is what lets the frames be fused,
 but not metric.  --max-depth, --voxel-size and --trunc are in those units (the nets' depth is 1 / disparity, between 0.1
 and 100).  The frames are decoded on the host, resized on the device as run_inference.py resizes them, and --intrinsics
@@ -98,6 +110,21 @@ parser.add_argument("--refine-group", default=1, type=int, metavar="G",
 parser.add_argument("--refine-max-dist", default=None, type=float, metavar="D",
                     help="a frame's point and the model's point pair up to this distance (the nets' units); default "
                          "the truncation distance")
+parser.add_argument("--consistency-weight", action='store_true',
+                    help="weigh every observation by the depth consistency of its pixel with the neighbouring fused frames "
+                         "(scsfm_hip.confidence); the disparities of all fused frames are kept on the device")
+parser.add_argument("--consistency-radius", default=None, type=int, metavar="R",
+                    help="fused frames on either side a frame is compared with, 1 .. 4 (default 1)")
+parser.add_argument("--consistency-reduce", default=None, choices=['mean', 'max'],
+                    help="a pixel's weight over its neighbours: their mean, as the training loss averages, or the best "
+                         "one, which is kinder to occlusions (default mean)")
+parser.add_argument("--consistency-min-views", default=None, type=int, metavar="N",
+                    help="a pixel that fewer neighbours can be compared with gets the weight 0 (default 1)")
+parser.add_argument("--consistency-floor", default=None, type=float, metavar="T",
+                    help="a weight below this becomes 0: the pixel is not fused (0 .. 1; default 0.0, nothing is cut)")
+parser.add_argument("--output-confidence", action='store_true',
+                    help="also write <output-dir>/confidence.npy and <output-dir>/confidence/*.png (needs "
+                         "--consistency-weight)")
 parser.add_argument("--output-dir", default='output', type=str, help="Output directory")
 
 
@@ -193,19 +220,22 @@ def relative_to(anchor_refined, anchor, poses):
     return torch.cat([R, t[:, :, None]], dim=2).contiguous()
 
 
-def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None, on_track=None):
+def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None, on_track=None, disps=None, weights=None):
     """Pass two with --refine-poses (see the module's docstring) -> the refined poses of all frames, float64 [n, 3, 4] on
-    the device.  The figures of the printed line are summed on the device, in float64, and read back once."""
+    the device.  The figures of the printed line are summed on the device, in float64, and read back once.  With
+    ``disps`` and ``weights`` (--consistency-weight: the stored disparities [n, 1, H, W] and the weights [n, H, W] of the
+    chosen frames) the net is not run again and every frame is integrated with its rows of the weights."""
     from scsfm_hip import tracking
     refined = c2w.clone()
     done = 0                                # chosen frames fused so far
     sums = torch.zeros(6, dtype=torch.float64, device=device)  # rms first / last (sum, frames), pair share, kept
 
-    def fuse(disp, imgs, idx, poses):
+    def fuse(disp, imgs, idx, poses, at):
         batch = (disp, imgs, poses.contiguous(), K_dev)
         if on_batch is not None:
             on_batch(*batch)
-        vol.integrate(*batch, is_disp=True, max_depth=args.max_depth)
+        vol.integrate(*batch, is_disp=True, max_depth=args.max_depth,
+                      weight=None if weights is None else weights[at:at + len(disp)])
         refined[idx] = poses
 
     for first, group in ((True, 1), (False, args.refine_group)):
@@ -213,11 +243,12 @@ def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None
         if not todo:
             continue
         for k, imgs, _ in frames([files[i] for i in todo], args, device, group):
-            disp = disp_net(imgs).contiguous()
+            at = k if first else 1 + k      # the group's place among the chosen frames
+            disp = disp_net(imgs).contiguous() if disps is None else disps[at:at + len(imgs)]
             ids = todo[k:k + len(imgs)]
             idx = torch.tensor(ids, device=device)
             if first:
-                fuse(disp, imgs, idx, c2w[idx])
+                fuse(disp, imgs, idx, c2w[idx], at)
                 continue
             anchor = chosen[done]               # the last frame before the group
             guess = relative_to(refined[anchor], c2w[anchor], c2w[idx])
@@ -226,7 +257,7 @@ def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None
             if on_track is not None:
                 on_track(ids, guess, got, disp)
             kept = tracking.kept_guess(got.report)
-            fuse(disp, imgs, idx, torch.where(kept[:, None, None], guess, got.c2w))
+            fuse(disp, imgs, idx, torch.where(kept[:, None, None], guess, got.c2w), at)
             done += len(ids)
             count, rr = got.report[:, :, 0], got.report[:, :, 1]
             for j, it in ((0, 0), (2, -1)):
@@ -250,13 +281,69 @@ def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None
     return refined
 
 
+def too_many_pixels(args, n, hw):
+    """--consistency-weight keeps n frames of hw on the device and weighs them in one call, whose sizes are ints"""
+    if args.consistency_weight and n * hw[0] * hw[1] > 2 ** 31 - 1:
+        raise SystemExit("--consistency-weight keeps the disparities of all {} fused frames of {} x {} on the device, and "
+                         "their pixels are more than 2^31 - 1: fuse fewer frames (a larger --every)".format(n, *hw))
+
+
+def consistency(args, disp_net, files, chosen, c2w, K_dev, hw, device, on_weights=None):
+    """The first half of pass two with --consistency-weight -> (the disparities float32 [n, 1, H, W], the weights float32
+    [n, H, W]) of the chosen frames, on the device.  The figures of the printed line are summed on the device, in
+    float64, and read back once."""
+    from scsfm_hip import confidence
+    n = len(chosen)
+    disps = torch.empty((n, 1) + tuple(hw), dtype=torch.float32, device=device)
+    print('disparities of {} frames kept on the device: {:.1f} MB'.format(n, disps.numel() * 4 / 1e6))
+    for k, imgs, _ in frames([files[i] for i in chosen], args, device, args.batch_size):
+        disps[k:k + len(imgs)] = disp_net(imgs)
+    idx = torch.tensor(chosen, device=device)
+    weight = confidence.weights(disps, c2w[idx].contiguous(), K_dev, radius=args.consistency_radius, is_disp=True,
+                                max_depth=args.max_depth, min_views=args.consistency_min_views,
+                                floor=args.consistency_floor, reduce=args.consistency_reduce)
+    if on_weights is not None:
+        on_weights(weight, disps)
+    total, zeros = torch.stack([weight.sum(dtype=torch.float64), (weight == 0).sum().double()]).tolist()
+    print('confidence of {} frames: mean {:.9g}, {:.9g} of the pixels at zero'.format(
+        n, total / weight.numel(), zeros / weight.numel()))
+    if args.output_confidence:
+        from PIL import Image
+        out_dir = os.path.join(args.output_dir, "confidence")
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(args.output_dir, "confidence.npy"), weight.cpu().numpy())
+        grey = (weight * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
+        for j, i in enumerate(chosen):
+            name = os.path.splitext(os.path.basename(str(files[i])))[0]
+            Image.fromarray(grey[j]).save(os.path.join(out_dir, name + ".png"))
+    return disps, weight
+
+
 @torch.no_grad()
-def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None):
-    """``on_poses(vec)``, ``on_batch(disp, imgs, c2w, K)``, ``on_render(result, views)`` and ``on_track(indices, guess,
-    track, disp)`` -- for the tests -- are handed the pose vectors [n - 1, 6], every fused batch's tensors, every rendered
-    batch's scsfm_hip.raycast.Cast with its poses [b, 3, 4], and every tracked group's frame indices, guessed poses
-    [g, 3, 4], scsfm_hip.tracking.Track and disparities, all on the device."""
+def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None, on_weights=None):
+    """``on_poses(vec)``, ``on_batch(disp, imgs, c2w, K)``, ``on_render(result, views)``, ``on_track(indices, guess,
+    track, disp)`` and ``on_weights(weight, disp)`` -- for the tests -- are handed the pose vectors [n - 1, 6], every fused
+    batch's tensors, every rendered batch's scsfm_hip.raycast.Cast with its poses [b, 3, 4], every tracked group's frame
+    indices, guessed poses [g, 3, 4], scsfm_hip.tracking.Track and disparities, and the weights [n, H, W] of
+    --consistency-weight with the stored disparities [n, 1, H, W] of the fused frames, all on the device."""
     args = parser.parse_args(argv)
+    given = [flag for flag, value in (("--consistency-radius", args.consistency_radius),
+                                      ("--consistency-reduce", args.consistency_reduce),
+                                      ("--consistency-min-views", args.consistency_min_views),
+                                      ("--consistency-floor", args.consistency_floor),
+                                      ("--output-confidence", args.output_confidence or None)) if value is not None]
+    if given and not args.consistency_weight:
+        raise SystemExit("{} needs --consistency-weight".format(given[0]))
+    args.consistency_radius = 1 if args.consistency_radius is None else args.consistency_radius
+    args.consistency_reduce = args.consistency_reduce or 'mean'
+    args.consistency_min_views = 1 if args.consistency_min_views is None else args.consistency_min_views
+    args.consistency_floor = 0.0 if args.consistency_floor is None else args.consistency_floor
+    if not 1 <= args.consistency_radius <= 4:
+        raise SystemExit("--consistency-radius must be between 1 and 4")
+    if args.consistency_min_views < 1:
+        raise SystemExit("--consistency-min-views must be at least 1")
+    if not 0.0 <= args.consistency_floor <= 1.0:
+        raise SystemExit("--consistency-floor must be between 0 and 1")
     if not 1 <= args.refine_iterations <= 64:
         raise SystemExit("--refine-iterations must be between 1 and 64")
     if args.refine_group < 1:
@@ -291,6 +378,9 @@ def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None)
     print('{} files to reconstruct from'.format(len(files)))
     if len(files) < 2:
         raise SystemExit("reconstruct.py needs at least two frames")
+    chosen = list(range(0, len(files), args.every))
+    if not args.no_resize:
+        too_many_pixels(args, len(chosen), (args.img_height, args.img_width))
     os.makedirs(args.output_dir, exist_ok=True)
 
     # pass one: the trajectory
@@ -304,6 +394,7 @@ def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None)
     if len(sizes) != 1:
         raise SystemExit("the frames of a reconstruction must all have one size")
     (stored_hw, used_hw), = sizes
+    too_many_pixels(args, len(chosen), used_hw)     # (again: with --no-resize the size is known only now)
     vec = torch.cat(vecs).float()
     if on_poses is not None:
         on_poses(vec)
@@ -326,16 +417,19 @@ def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None)
     K_dev = torch.from_numpy(K).to(device)
 
     # pass two: the depth of every N-th frame, fused batch by batch on the device
-    chosen = list(range(0, len(files), args.every))
+    disps = weights = None
+    if args.consistency_weight:
+        disps, weights = consistency(args, disp_net, files, chosen, c2w, K_dev, used_hw, device, on_weights)
     if args.refine_poses:
-        c2w = refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch, on_track)
+        c2w = refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch, on_track, disps, weights)
     for k, imgs, _ in () if args.refine_poses else frames([files[i] for i in chosen], args, device, args.batch_size):
-        disp = disp_net(imgs)
+        disp = disp_net(imgs) if disps is None else disps[k:k + len(imgs)]
         idx = torch.tensor(chosen[k:k + len(imgs)], device=device)
         batch = (disp.contiguous(), imgs, c2w[idx].contiguous(), K_dev)
         if on_batch is not None:
             on_batch(*batch)
-        vol.integrate(*batch, is_disp=True, max_depth=args.max_depth)
+        vol.integrate(*batch, is_disp=True, max_depth=args.max_depth,
+                      weight=None if weights is None else weights[k:k + len(imgs)])
     xyz, rgb = vol.extract(args.min_weight)
     path = os.path.join(args.output_dir, "reconstruction.ply")
     fusion.write_ply(path, xyz, rgb)

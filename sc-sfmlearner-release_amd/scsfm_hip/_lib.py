@@ -21,9 +21,9 @@ import threading
 # hipErrorNoDevice.)
 import torch  # noqa: F401  (must precede ctypes.CDLL below)
 
-from .libraries import ALL, BY_NAME, CATALOGUE, EVERY, HERE, LATER, LIBRARIES, REGISTRY, ROWS, SUMMARY, TABLE  # noqa: F401  (ALL, CATALOGUE, EVERY, HERE, LATER, LIBRARIES, ROWS: as before)
+from .libraries import ALL, BY_NAME, CATALOGUE, EVERY, HERE, LATER, LIBRARIES, REGISTRY, ROWS, SINCE, SUMMARY, TABLE  # noqa: F401  (ALL, CATALOGUE, EVERY, HERE, LATER, LIBRARIES, ROWS: as before)
 
-__doc__ = (__doc__ or "") + SUMMARY + "\n"
+__doc__ = (__doc__ or "") + SUMMARY + "\n" + SINCE + "\n"
 
 HEADER = BY_NAME[""].header
 # SCSFM_HIP_LIB points at a library built elsewhere (tuning variants, a system-wide install)

@@ -31,9 +31,9 @@ import subprocess
 import sys
 import tempfile
 
-from .libraries import ALL, BY_NAME, CATALOGUE, EVERY, HERE, INCLUDE, LATER, LIBRARIES, REGISTRY, ROWS, SUMMARY, TABLE, find  # noqa: F401  (ALL, CATALOGUE, EVERY, LATER, LIBRARIES, ROWS: as before)
+from .libraries import ALL, BY_NAME, CATALOGUE, EVERY, HERE, INCLUDE, LATER, LIBRARIES, REGISTRY, ROWS, SINCE, SUMMARY, TABLE, find  # noqa: F401  (ALL, CATALOGUE, EVERY, LATER, LIBRARIES, ROWS: as before)
 
-__doc__ = (__doc__ or "") + SUMMARY + "\n"
+__doc__ = (__doc__ or "") + SUMMARY + "\n" + SINCE + "\n"
 
 CSRC = BY_NAME[""].csrc
 LIB = BY_NAME[""].lib

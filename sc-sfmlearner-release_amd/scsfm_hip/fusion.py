@@ -112,10 +112,16 @@ class Volume:
     def colour(self):
         return self.planes[2:]
 
-    def integrate(self, disp_or_depth, images, c2w, K, is_disp=True, near=0.0, max_depth=10.0):
+    def integrate(self, disp_or_depth, images, c2w, K, is_disp=True, near=0.0, max_depth=10.0, weight=None):
         """Integrates F frames, in launches of ``frames_per_launch``: the nets' disparity (``is_disp``) or a depth
         [F, 1, H, W] / [F, H, W], the normalised images [F, 3, H, W] or None, the camera-to-world poses float64
-        [F, 3, 4] and the intrinsics float32 [3, 3] of these H x W frames."""
+        [F, 3, 4] and the intrinsics float32 [3, 3] of these H x W frames.  With ``weight`` (float32 [F, H, W], what
+        scsfm_hip.confidence.weights gives) every observation counts by its pixel's weight instead of 1
+        (scsfm_hip.confidence.integrate, libscsfm_conf.so)."""
+        if weight is not None:
+            from . import confidence
+            return confidence.integrate(self, disp_or_depth, images, c2w, K, weight, is_disp=is_disp, near=near,
+                                        max_depth=max_depth)
         d = _check("disp_or_depth", disp_or_depth, torch.float32)
         if d.dim() == 4 and d.shape[1] == 1:
             d = d[:, 0]

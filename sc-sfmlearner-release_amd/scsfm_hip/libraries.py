@@ -11,8 +11,8 @@ as ``EVERY + NEXT`` with twenty rows, is those five, so rows added since stand i
 as ``ALL + BEYOND`` with twenty-one rows, is those six, and ``SUMMARY`` lists them, one line each, pinned too; so rows added
 since stand in ``FURTHER``.  ``CATALOGUE``, pinned as ``LIBRARIES + FURTHER`` with twenty-two rows, is those seven.
 
-``ADDED`` ends the ratchet: it is the open-ended tuple.  Every library added from libscsfm_track.so on is appended to
-it, and no test pins its length or its contents -- a test asserts that its own row is in it.  ``REGISTRY`` is
+``ADDED`` ends the ratchet: it is the open-ended tuple.  Every library added from libscsfm_track.so on (libscsfm_conf.so
+is the second) is appended to it, and no test pins its length or its contents -- a test asserts that its own row is in it.  ``REGISTRY`` is
 ``CATALOGUE + ADDED``, every row: the loops that build, load and name the libraries run over it, and ``find(name)`` looks
 a row up among all of them.  Imports nothing but os, so that scsfm_hip._lib can read it on import.
 """
@@ -113,6 +113,8 @@ CATALOGUE = LIBRARIES + FURTHER
 ADDED = (
     Library("track", 1, "track:build", "the frame-to-model tracking of predicted depth against the ray-cast model by "
                                        "point-to-plane ICP (reconstruct.py --refine-poses)"),
+    Library("conf", 1, "conf:build", "the depth consistency of a frame with its neighbours as a per-pixel confidence and "
+                                     "the TSDF fusion weighed by it (reconstruct.py --consistency-weight)"),
 )
 REGISTRY = CATALOGUE + ADDED
 _FIND = {row.name: row for row in REGISTRY}
@@ -127,3 +129,7 @@ def find(name):
 # include/scsfm_cast.h)
 SUMMARY = "\n".join(f"    {os.path.basename(row.lib):22s} {os.path.basename(row.csrc) + '/':14s} "
                     f"include/{os.path.basename(row.header):16s} {row.what}" for row in LIBRARIES)
+# the same lines for the rows added since SUMMARY was fixed (FURTHER and ADDED: cast, track, conf, ...), appended to those
+# docstrings behind it
+SINCE = "\n".join(f"    {os.path.basename(row.lib):22s} {os.path.basename(row.csrc) + '/':14s} "
+                  f"include/{os.path.basename(row.header):16s} {row.what}" for row in FURTHER + ADDED)
