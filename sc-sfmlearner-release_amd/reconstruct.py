@@ -45,6 +45,21 @@ the frames ahead are not refined yet), and the alignment itself stays unweighted
 <output-dir>/confidence.npy (float32 [n, H, W]) and <output-dir>/confidence/<frame name>.png (8-bit grey).  Without
 --consistency-weight every file and printed line is what it was.
 
+With --follow the volume has a fixed size and moves with the camera (scsfm_hip.rolling, libscsfm_roll.so: KinectFusion's
+moving volume), so memory is set by --max-depth and not by the length of the path, and a sequence of any length is fused at
+one --voxel-size, which the flag requires.  The window is --follow-dims voxels (default a cube of side
+2 (max-depth + trunc) / voxel-size + 2 step, rounded up to a multiple of 8) on a lattice fixed by its first corner, which
+centres the first batch's middle camera.  Before each batch of pass two (each group under --refine-poses) the window is
+placed from the camera centre of the batch's frame len // 2 -- the chain's pose, from the host copy that poses.txt is
+written from, or under --refine-poses the group's guessed pose, one copy of 96 bytes per group -- and moves in whole
+multiples of --follow-step voxels once that camera's cell is a step or more from the central cell.  The surface points
+whose edges leave the window are extracted first and copied to the host, the planes are shifted, what enters is empty, and
+space that was left is not entered again.  reconstruction.ply is the streamed points in the order of the shifts followed by
+the points still in the window at the end; every edge of the lattice gives at most one point.  --consistency-weight works
+unchanged (its weights do not depend on the volume).  --mesh, --render and --render-poses are refused beside --follow: a
+mesh stitched over windows and casts of a volume that has moved on are not built.  Without --follow every file and printed
+line is what it was.
+
 Units: the predictions have the nets' own scale -- consistent along the sequence, which is what lets the frames be fused,
 but not metric.  --max-depth, --voxel-size and --trunc are in those units (the nets' depth is 1 / disparity, between 0.1
 and 100).  The frames are decoded on the host, resized on the device as run_inference.py resizes them, and --intrinsics
@@ -125,6 +140,14 @@ parser.add_argument("--consistency-floor", default=None, type=float, metavar="T"
 parser.add_argument("--output-confidence", action='store_true',
                     help="also write <output-dir>/confidence.npy and <output-dir>/confidence/*.png (needs "
                          "--consistency-weight)")
+parser.add_argument("--follow", action='store_true',
+                    help="a volume of fixed size that moves with the camera (scsfm_hip.rolling); needs --voxel-size; the "
+                         "points that leave are streamed into reconstruction.ply")
+parser.add_argument("--follow-dims", default=None, type=int, nargs=3, metavar=("NX", "NY", "NZ"),
+                    help="voxels of the moving window (default a cube of side 2 (max-depth + trunc) / voxel-size + 2 "
+                         "step, rounded up to a multiple of 8)")
+parser.add_argument("--follow-step", default=None, type=int, metavar="N",
+                    help="the window moves in whole multiples of this many voxels (default 8)")
 parser.add_argument("--output-dir", default='output', type=str, help="Output directory")
 
 
@@ -220,11 +243,14 @@ def relative_to(anchor_refined, anchor, poses):
     return torch.cat([R, t[:, :, None]], dim=2).contiguous()
 
 
-def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None, on_track=None, disps=None, weights=None):
+def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None, on_track=None, disps=None, weights=None,
+           follow=None):
     """Pass two with --refine-poses (see the module's docstring) -> the refined poses of all frames, float64 [n, 3, 4] on
     the device.  The figures of the printed line are summed on the device, in float64, and read back once.  With
     ``disps`` and ``weights`` (--consistency-weight: the stored disparities [n, 1, H, W] and the weights [n, H, W] of the
-    chosen frames) the net is not run again and every frame is integrated with its rows of the weights."""
+    chosen frames) the net is not run again and every frame is integrated with its rows of the weights.  ``follow``
+    (--follow) is handed the pose the window is placed from before every group is tracked: the first frame's chained pose,
+    then each group's middle guess."""
     from scsfm_hip import tracking
     refined = c2w.clone()
     done = 0                                # chosen frames fused so far
@@ -248,10 +274,14 @@ def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None
             ids = todo[k:k + len(imgs)]
             idx = torch.tensor(ids, device=device)
             if first:
+                if follow is not None:
+                    follow(c2w[ids[0]])
                 fuse(disp, imgs, idx, c2w[idx], at)
                 continue
             anchor = chosen[done]               # the last frame before the group
             guess = relative_to(refined[anchor], c2w[anchor], c2w[idx])
+            if follow is not None:
+                follow(guess[len(ids) // 2])
             got = vol.track(disp, guess, K_dev, is_disp=True, max_depth=args.max_depth,
                             iterations=args.refine_iterations, max_dist=args.refine_max_dist)
             if on_track is not None:
@@ -319,14 +349,60 @@ def consistency(args, disp_net, files, chosen, c2w, K_dev, hw, device, on_weight
     return disps, weight
 
 
+# Voxels the window of --follow moves by, in whole multiples.  A larger step means fewer, equally expensive shifts and a
+# window 2 step voxels wider on every axis.  Measured (tools/bench_rolling.py, profiles/rolling_bench.json: a generated drive
+# of 256 frames of 256 x 832 through a window of 184 voxels a side, batches of 8, medians of 15): at 8 the 31 shifts cost
+# 0.12 ms each, the count's trip to the host and the points' copy included, 61 % of a pass two WITHOUT nets (6.25 ms); once
+# the disparity net runs between two shifts that is a few per cent, so 8 stays, and a step of 16 would halve it for a window
+# 16 voxels wider, which is unmeasured.
+FOLLOW_STEP = 8
+
+
+def follow_arguments(args):
+    """--follow's flags, checked and completed before anything is loaded: args.follow_step and args.follow_dims are set"""
+    given = [flag for flag, value in (("--follow-dims", args.follow_dims), ("--follow-step", args.follow_step))
+             if value is not None]
+    if given and not args.follow:
+        raise SystemExit("{} needs --follow".format(given[0]))
+    args.follow_step = FOLLOW_STEP if args.follow_step is None else args.follow_step
+    if not args.follow:
+        return
+    if args.voxel_size is None:
+        raise SystemExit("--follow needs --voxel-size: the lattice of a moving volume is fixed before the path is known")
+    if not (args.voxel_size > 0 and np.isfinite(args.voxel_size)):
+        raise SystemExit("--voxel-size must be positive")
+    for flag, value in (("--mesh", args.mesh), ("--render-poses", args.render_poses is not None), ("--render", args.render)):
+        if value:
+            raise SystemExit("--follow cannot be combined with {}: the volume has moved on from what left it".format(flag))
+    if args.follow_step < 1:
+        raise SystemExit("--follow-step must be at least 1")
+    if args.follow_dims is None:
+        from scsfm_hip.fusion import TRUNC_VOXELS    # (imports torch and the table of libraries; loads none)
+        trunc = TRUNC_VOXELS * args.voxel_size if args.trunc is None else args.trunc
+        side = 2.0 * (args.max_depth + trunc) / args.voxel_size + 2 * args.follow_step
+        if not side < 2 ** 31:
+            raise SystemExit("--follow: a window of {:.6g} voxels a side is above the limit of 2^29 voxels: choose a "
+                             "larger --voxel-size or give --follow-dims".format(side))
+        args.follow_dims = [max(8, 8 * int(np.ceil(side / 8.0)))] * 3
+    if min(args.follow_dims) < 1:
+        raise SystemExit("--follow-dims must all be at least 1")
+    if args.follow_dims[0] * args.follow_dims[1] * args.follow_dims[2] > 2 ** 29:
+        raise SystemExit("--follow-dims: a window of {} x {} x {} voxels is above the limit of 2^29: choose a larger "
+                         "--voxel-size or smaller --follow-dims".format(*args.follow_dims))
+
+
 @torch.no_grad()
-def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None, on_weights=None):
+def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None, on_weights=None, on_shift=None):
     """``on_poses(vec)``, ``on_batch(disp, imgs, c2w, K)``, ``on_render(result, views)``, ``on_track(indices, guess,
     track, disp)`` and ``on_weights(weight, disp)`` -- for the tests -- are handed the pose vectors [n - 1, 6], every fused
     batch's tensors, every rendered batch's scsfm_hip.raycast.Cast with its poses [b, 3, 4], every tracked group's frame
     indices, guessed poses [g, 3, 4], scsfm_hip.tracking.Track and disparities, and the weights [n, H, W] of
-    --consistency-weight with the stored disparities [n, 1, H, W] of the fused frames, all on the device."""
+    --consistency-weight with the stored disparities [n, 1, H, W] of the fused frames, all on the device.
+    ``on_shift(shift, offset, xyz, rgb)`` is handed every move of --follow's window: the shift in voxels, the window's
+    offset after it, and the points that left with it, on the device; it is called before the ``on_batch`` of the batch
+    the window was moved for."""
     args = parser.parse_args(argv)
+    follow_arguments(args)
     given = [flag for flag, value in (("--consistency-radius", args.consistency_radius),
                                       ("--consistency-reduce", args.consistency_reduce),
                                       ("--consistency-min-views", args.consistency_min_views),
@@ -399,21 +475,46 @@ def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None,
     if on_poses is not None:
         on_poses(vec)
     c2w = chain_poses(vec, args.rotation_mode).contiguous()  # float64 [n, 3, 4], on the device
-    np.savetxt(os.path.join(args.output_dir, "poses.txt"), c2w.reshape(-1, 12).cpu().numpy(), delimiter=' ', fmt='%1.8e')
+    chain = c2w.reshape(-1, 12).cpu().numpy()
+    np.savetxt(os.path.join(args.output_dir, "poses.txt"), chain, delimiter=' ', fmt='%1.8e')
     K = scaled_intrinsics(np.genfromtxt(args.intrinsics), stored_hw, used_hw)
 
+    streamed, follow = [], None
+    if args.follow:
+        # the window: its first corner centres the middle camera of the first batch (under --refine-poses the first frame)
+        from scsfm_hip import rolling
+        dims, voxel = tuple(args.follow_dims), args.voxel_size
+        middle = chosen[0] if args.refine_poses else chosen[min(args.batch_size, len(chosen)) // 2]
+        origin = rolling.initial_origin(chain[middle].reshape(3, 4)[:, 3], dims, voxel)
+        print('window: {} x {} x {} voxels of {:.6g}, {:.1f} MB, first corner ({:.4g}, {:.4g}, {:.4g})'.format(
+            *dims, voxel, 40 * dims[0] * dims[1] * dims[2] / 1e6, *origin))
+        vol = rolling.RollingVolume(dims, origin, voxel, args.trunc, device=device,
+                                    frames_per_launch=args.frames_per_launch or fusion.FRAMES_PER_LAUNCH)
+
+        def follow(pose):
+            """places the window for the camera of ``pose`` ([3, 4], a host array or a device tensor: 96 bytes)"""
+            pose = pose.cpu().numpy() if isinstance(pose, torch.Tensor) else pose
+            shift = rolling.shift_for(pose.reshape(3, 4)[:, 3], vol.origin0, vol.offset, vol.dims, vol.voxel,
+                                      args.follow_step)
+            if any(shift):
+                xyz, rgb = vol.shift(shift, args.min_weight)
+                if on_shift is not None:
+                    on_shift(shift, vol.offset, xyz, rgb)
+                streamed.append((xyz.cpu().numpy(), rgb.cpu().numpy()))
+
     # the box
-    lo, hi = fusion.camera_box(c2w, args.max_depth)
-    voxel = args.voxel_size if args.voxel_size is not None else float((hi - lo).max()) / (args.resolution or 256)
-    origin, dims = fusion.bounds_from_cameras(c2w, args.max_depth, voxel)
-    nvox = dims[0] * dims[1] * dims[2]
-    print('volume: {} x {} x {} voxels of {:.6g}, {:.1f} MB, corner ({:.4g}, {:.4g}, {:.4g})'.format(
-        *dims, voxel, 20 * nvox / 1e6, *origin))
-    if nvox > fusion.MAX_VOXELS:
-        raise SystemExit("a volume of {} voxels is above the limit of 2^29: choose a larger --voxel-size (or a smaller "
-                         "--resolution or --max-depth)".format(nvox))
-    vol = fusion.Volume(dims, origin, voxel, args.trunc, device=device,
-                        frames_per_launch=args.frames_per_launch or fusion.FRAMES_PER_LAUNCH)
+    if not args.follow:
+        lo, hi = fusion.camera_box(c2w, args.max_depth)
+        voxel = args.voxel_size if args.voxel_size is not None else float((hi - lo).max()) / (args.resolution or 256)
+        origin, dims = fusion.bounds_from_cameras(c2w, args.max_depth, voxel)
+        nvox = dims[0] * dims[1] * dims[2]
+        print('volume: {} x {} x {} voxels of {:.6g}, {:.1f} MB, corner ({:.4g}, {:.4g}, {:.4g})'.format(
+            *dims, voxel, 20 * nvox / 1e6, *origin))
+        if nvox > fusion.MAX_VOXELS:
+            raise SystemExit("a volume of {} voxels is above the limit of 2^29: choose a larger --voxel-size (or a smaller "
+                             "--resolution or --max-depth)".format(nvox))
+        vol = fusion.Volume(dims, origin, voxel, args.trunc, device=device,
+                            frames_per_launch=args.frames_per_launch or fusion.FRAMES_PER_LAUNCH)
     K_dev = torch.from_numpy(K).to(device)
 
     # pass two: the depth of every N-th frame, fused batch by batch on the device
@@ -421,19 +522,28 @@ def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None,
     if args.consistency_weight:
         disps, weights = consistency(args, disp_net, files, chosen, c2w, K_dev, used_hw, device, on_weights)
     if args.refine_poses:
-        c2w = refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch, on_track, disps, weights)
+        c2w = refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch, on_track, disps, weights, follow)
     for k, imgs, _ in () if args.refine_poses else frames([files[i] for i in chosen], args, device, args.batch_size):
         disp = disp_net(imgs) if disps is None else disps[k:k + len(imgs)]
         idx = torch.tensor(chosen[k:k + len(imgs)], device=device)
         batch = (disp.contiguous(), imgs, c2w[idx].contiguous(), K_dev)
+        if follow is not None:
+            follow(chain[chosen[k + len(imgs) // 2]])
         if on_batch is not None:
             on_batch(*batch)
         vol.integrate(*batch, is_disp=True, max_depth=args.max_depth,
                       weight=None if weights is None else weights[k:k + len(imgs)])
     xyz, rgb = vol.extract(args.min_weight)
     path = os.path.join(args.output_dir, "reconstruction.ply")
+    if args.follow:
+        out = sum(len(p[0]) for p in streamed)
+        xyz = np.concatenate([p[0] for p in streamed] + [xyz.cpu().numpy()])
+        rgb = np.concatenate([p[1] for p in streamed] + [rgb.cpu().numpy()])
     fusion.write_ply(path, xyz, rgb)
     print('{} surface points from {} frames -> {}'.format(len(xyz), len(chosen), path))
+    if args.follow:
+        print('the window moved {} times to offset ({}, {}, {}); {} of the points were streamed out on the way'.format(
+            len(streamed), *vol.offset, out))
     if args.mesh:
         from scsfm_hip import meshing
         path = os.path.join(args.output_dir, "mesh.ply")
