@@ -33,6 +33,17 @@ frame that never finds enough pairs, or a well-conditioned system, keeps its gue
 <output-dir>/poses_refined.txt has the same format (a frame that is not fused follows the refined frame before it by the
 chain's relative motion), and reconstruction.ply, mesh.ply and the casts of --render are of the refined model and poses.
 
+With --refine-scale (beside --refine-poses) the alignment has a seventh degree of freedom, the scale of the frame's own
+depth (scsfm_hip.similarity, libscsfm_sim3.so): the nets' depth is only softly scale-consistent along a sequence, and a
+rigid tracker trades a frame whose depth is a few per cent too long or too short for a wrong pose.  The first fused frame
+has scale 1 and is not tracked; a group starts from the scale of the last frame fused before it; every frame is integrated
+from its scaled depth (as a depth) at its refined pose, and a frame that kept its guess keeps its starting scale too.  In
+an iteration whose scale pivot ratio is not above --refine-scale-pivot -- a frame that sees nothing but planes -- the scale
+is held and the step is the rigid one.  <output-dir>/scales_refined.txt holds one scale per frame ('%1.8e'; a frame that is
+not fused follows the fused frame before it), one more line is printed, and --render's |pred - fused| / fused compares the
+scaled prediction.  --consistency-weight keeps computing its weights from the unscaled chain, and --follow works
+unchanged.  Without --refine-scale every file and printed line is what it was.
+
 With --consistency-weight every observation enters the volume with the depth consistency of its pixel as its weight
 (scsfm_hip.confidence, libscsfm_conf.so): pass two first runs the disparity net over all fused frames and keeps the
 disparities on the device, every frame is compared with its --consistency-radius neighbours on either side among the fused
@@ -125,6 +136,12 @@ parser.add_argument("--refine-group", default=1, type=int, metavar="G",
 parser.add_argument("--refine-max-dist", default=None, type=float, metavar="D",
                     help="a frame's point and the model's point pair up to this distance (the nets' units); default "
                          "the truncation distance")
+parser.add_argument("--refine-scale", action='store_true',
+                    help="also refine a scale of every fused frame's depth: ICP over seven degrees of freedom "
+                         "(scsfm_hip.similarity); needs --refine-poses; also writes <output-dir>/scales_refined.txt")
+parser.add_argument("--refine-scale-pivot", default=None, type=float, metavar="P",
+                    help="a frame's scale is solved in an iteration whose scale pivot ratio is above this and held "
+                         "otherwise; needs --refine-scale (default scsfm_hip.similarity.MIN_SCALE_PIVOT, 2e-3)")
 parser.add_argument("--consistency-weight", action='store_true',
                     help="weigh every observation by the depth consistency of its pixel with the neighbouring fused frames "
                          "(scsfm_hip.confidence); the disparities of all fused frames are kept on the device")
@@ -186,10 +203,11 @@ def read_poses(path):
     return poses.reshape(-1, 3, 4)
 
 
-def render(args, vol, disp_net, views, K_dev, hw, device, names, files=None, on_render=None):
+def render(args, vol, disp_net, views, K_dev, hw, device, names, files=None, on_render=None, scales=None):
     """The third pass: casts ``views`` (float64 [n, 3, 4] on the device) in batches and writes fused_depth.npy and the
     pictures.  With ``files`` (the fused frames, one per view) the disparity net runs again batch by batch and the
-    agreement of its depth with the fused one is summed on the device, in float64, and read back once."""
+    agreement of its depth with the fused one is summed on the device, in float64, and read back once; with ``scales``
+    (--refine-scale: float64 [n], one per view) the depth compared is the scaled one that was fused."""
     from PIL import Image
 
     from scsfm_hip import raycast
@@ -211,7 +229,12 @@ def render(args, vol, disp_net, views, K_dev, hw, device, names, files=None, on_
         if preds is not None:
             k0, imgs, _ = next(preds)
             assert k0 == k and len(imgs) == len(batch)
-            pred = 1.0 / disp_net(imgs)[:, 0]
+            if scales is None:
+                pred = 1.0 / disp_net(imgs)[:, 0]
+            else:   # (--refine-scale: the prediction as it was fused)
+                from scsfm_hip import similarity
+                pred = similarity.scaled_depth(disp_net(imgs).contiguous(), scales[k:k + len(batch)].contiguous(),
+                                               is_disp=True)[:, 0]
             both = hit & (pred <= args.max_depth)
             ratio = (pred.double() - got.depth.double()).abs() / got.depth.double()
             sums[1] += both.sum()
@@ -250,17 +273,27 @@ def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None
     ``disps`` and ``weights`` (--consistency-weight: the stored disparities [n, 1, H, W] and the weights [n, H, W] of the
     chosen frames) the net is not run again and every frame is integrated with its rows of the weights.  ``follow``
     (--follow) is handed the pose the window is placed from before every group is tracked: the first frame's chained pose,
-    then each group's middle guess."""
+    then each group's middle guess.  With --refine-scale the return value is (the refined poses, the refined scales of
+    all frames, float64 [n] on the device): every frame carries a scale of its depth, a group starts from the scale of the
+    last frame fused before it, is aligned over seven degrees of freedom (scsfm_hip.similarity) and is integrated from
+    the scaled depth, as a depth."""
     from scsfm_hip import tracking
+    if args.refine_scale:
+        from scsfm_hip import similarity
+        scales = torch.ones(len(c2w), dtype=torch.float64, device=device)
+        pivot = similarity.MIN_SCALE_PIVOT if args.refine_scale_pivot is None else args.refine_scale_pivot
+        held = torch.zeros(1, dtype=torch.float64, device=device)   # frames whose scale was held throughout
     refined = c2w.clone()
     done = 0                                # chosen frames fused so far
     sums = torch.zeros(6, dtype=torch.float64, device=device)  # rms first / last (sum, frames), pair share, kept
 
     def fuse(disp, imgs, idx, poses, at):
+        if args.refine_scale:   # the depth the tracker saw, as a depth
+            disp = similarity.scaled_depth(disp, scales[idx], is_disp=True)
         batch = (disp, imgs, poses.contiguous(), K_dev)
         if on_batch is not None:
             on_batch(*batch)
-        vol.integrate(*batch, is_disp=True, max_depth=args.max_depth,
+        vol.integrate(*batch, is_disp=not args.refine_scale, max_depth=args.max_depth,
                       weight=None if weights is None else weights[at:at + len(disp)])
         refined[idx] = poses
 
@@ -282,11 +315,20 @@ def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None
             guess = relative_to(refined[anchor], c2w[anchor], c2w[idx])
             if follow is not None:
                 follow(guess[len(ids) // 2])
-            got = vol.track(disp, guess, K_dev, is_disp=True, max_depth=args.max_depth,
-                            iterations=args.refine_iterations, max_dist=args.refine_max_dist)
+            if args.refine_scale:
+                scale0 = scales[anchor].expand(len(ids)).contiguous()
+                got = vol.track_scaled(disp, guess, scale0, K_dev, is_disp=True, max_depth=args.max_depth,
+                                       iterations=args.refine_iterations, max_dist=args.refine_max_dist,
+                                       min_scale_pivot=pivot)
+                kept = similarity.kept_guess(got.report)
+                scales[idx] = torch.where(kept, scale0, got.scale)
+                held += similarity.held_scale(got.report).sum()
+            else:
+                got = vol.track(disp, guess, K_dev, is_disp=True, max_depth=args.max_depth,
+                                iterations=args.refine_iterations, max_dist=args.refine_max_dist)
+                kept = tracking.kept_guess(got.report)
             if on_track is not None:
                 on_track(ids, guess, got, disp)
-            kept = tracking.kept_guess(got.report)
             fuse(disp, imgs, idx, torch.where(kept[:, None, None], guess, got.c2w), at)
             done += len(ids)
             count, rr = got.report[:, :, 0], got.report[:, :, 1]
@@ -308,6 +350,21 @@ def refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch=None
     print('refined {} poses -> {}: mean rms residual {:.12g} -> {:.12g}, mean pair share {:.12g}, {} frames kept their '
           'guess'.format(n, path, first_sum / first_n if first_n else float("nan"),
                          last_sum / last_n if last_n else float("nan"), share / n if n else float("nan"), int(kept)))
+    if args.refine_scale:
+        # a frame that is not fused follows the fused frame before it
+        for a, b in zip(chosen, chosen[1:] + [len(c2w)]):
+            scales[a + 1:b] = scales[a]
+        path = os.path.join(args.output_dir, "scales_refined.txt")
+        np.savetxt(path, scales.cpu().numpy(), fmt='%1.8e')
+        tracked = scales[torch.tensor(chosen[1:], dtype=torch.long, device=device)]
+        if n:
+            low, mean, high, n_held = torch.stack([tracked.min(), tracked.mean(), tracked.max(), held[0]]).tolist()
+        else:
+            low = mean = high = float("nan")
+            n_held = 0
+        print('refined {} scales -> {}: min {:.12g}, mean {:.12g}, max {:.12g}, {} frames held their scale '
+              'throughout'.format(n, path, low, mean, high, int(n_held)))
+        return refined, scales
     return refined
 
 
@@ -400,7 +457,8 @@ def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None,
     --consistency-weight with the stored disparities [n, 1, H, W] of the fused frames, all on the device.
     ``on_shift(shift, offset, xyz, rgb)`` is handed every move of --follow's window: the shift in voxels, the window's
     offset after it, and the points that left with it, on the device; it is called before the ``on_batch`` of the batch
-    the window was moved for."""
+    the window was moved for.  With --refine-scale ``on_batch``'s first tensor is the scaled depth that is integrated
+    and ``on_track``'s track a scsfm_hip.similarity.Track."""
     args = parser.parse_args(argv)
     follow_arguments(args)
     given = [flag for flag, value in (("--consistency-radius", args.consistency_radius),
@@ -426,6 +484,12 @@ def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None,
         raise SystemExit("--refine-group must be at least 1")
     if args.refine_max_dist is not None and not (args.refine_max_dist > 0 and np.isfinite(args.refine_max_dist)):
         raise SystemExit("--refine-max-dist must be positive")
+    if args.refine_scale and not args.refine_poses:
+        raise SystemExit("--refine-scale needs --refine-poses")
+    if args.refine_scale_pivot is not None and not args.refine_scale:
+        raise SystemExit("--refine-scale-pivot needs --refine-scale")
+    if args.refine_scale_pivot is not None and not args.refine_scale_pivot > 0:
+        raise SystemExit("--refine-scale-pivot must be positive")
     novel = read_poses(args.render_poses) if args.render_poses is not None else None
     if args.render_step is not None and not (args.render_step > 0 and np.isfinite(args.render_step)):
         raise SystemExit("--render-step must be positive")
@@ -521,8 +585,11 @@ def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None,
     disps = weights = None
     if args.consistency_weight:
         disps, weights = consistency(args, disp_net, files, chosen, c2w, K_dev, used_hw, device, on_weights)
+    scales = None
     if args.refine_poses:
         c2w = refine(args, vol, disp_net, files, chosen, c2w, K_dev, device, on_batch, on_track, disps, weights, follow)
+        if args.refine_scale:
+            c2w, scales = c2w
     for k, imgs, _ in () if args.refine_poses else frames([files[i] for i in chosen], args, device, args.batch_size):
         disp = disp_net(imgs) if disps is None else disps[k:k + len(imgs)]
         idx = torch.tensor(chosen[k:k + len(imgs)], device=device)
@@ -557,7 +624,7 @@ def main(argv=None, on_poses=None, on_batch=None, on_render=None, on_track=None,
         fused = [files[i] for i in chosen]
         names = [os.path.splitext(os.path.basename(str(f)))[0] for f in fused]
         render(args, vol, disp_net, c2w[torch.tensor(chosen, device=device)], K_dev, used_hw, device, names, files=fused,
-               on_render=on_render)
+               on_render=on_render, scales=None if scales is None else scales[torch.tensor(chosen, device=device)])
     return vol
 
 

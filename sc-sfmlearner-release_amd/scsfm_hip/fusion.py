@@ -179,6 +179,13 @@ class Volume:
         from . import tracking
         return tracking.track(self, depth_or_disp, guess, K, **kwargs)
 
+    def track_scaled(self, depth_or_disp, guess, scale0, K, **kwargs):
+        """-> similarity.Track(c2w float64 [V, 3, 4], scale float64 [V], report, model_depth, model_normal, state) on the
+        device: the poses ``guess`` and the depth scales ``scale0`` of V frames refined against this volume by
+        point-to-plane ICP over seven degrees of freedom (scsfm_hip.similarity.track, libscsfm_sim3.so)."""
+        from . import similarity
+        return similarity.track(self, depth_or_disp, guess, scale0, K, **kwargs)
+
 
 def camera_box(c2w, max_depth):
     """The box of the camera centres grown by ``max_depth`` on every side -> (lo, hi), two float64 arrays of 3.

@@ -12,7 +12,7 @@ as ``ALL + BEYOND`` with twenty-one rows, is those six, and ``SUMMARY`` lists th
 since stand in ``FURTHER``.  ``CATALOGUE``, pinned as ``LIBRARIES + FURTHER`` with twenty-two rows, is those seven.
 
 ``ADDED`` ends the ratchet: it is the open-ended tuple.  Every library added from libscsfm_track.so on (libscsfm_conf.so
-is the second, libscsfm_roll.so the third) is appended to it, and no test pins its length or its contents -- a test asserts that its own row is in it.  ``REGISTRY`` is
+is the second, libscsfm_roll.so the third, libscsfm_sim3.so the fourth) is appended to it, and no test pins its length or its contents -- a test asserts that its own row is in it.  ``REGISTRY`` is
 ``CATALOGUE + ADDED``, every row: the loops that build, load and name the libraries run over it, and ``find(name)`` looks
 a row up among all of them.  Imports nothing but os, so that scsfm_hip._lib can read it on import.
 """
@@ -117,6 +117,9 @@ ADDED = (
                                      "the TSDF fusion weighed by it (reconstruct.py --consistency-weight)"),
     Library("roll", 1, "roll:build", "the shift of a volume that follows the camera by whole voxels and the surface points "
                                      "that leave with it (reconstruct.py --follow)"),
+    Library("sim3", 1, "sim3:build", "the frame-to-model tracking of predicted depth with a scale of its own per frame: "
+                                     "point-to-plane ICP over seven degrees of freedom, the scale solved only where it is "
+                                     "observable (reconstruct.py --refine-scale)"),
 )
 REGISTRY = CATALOGUE + ADDED
 _FIND = {row.name: row for row in REGISTRY}
