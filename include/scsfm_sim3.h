@@ -5,8 +5,9 @@
  * logarithm of the frame's depth scale.  A projective association per pixel, 37 double-precision sums per frame, a 7 x 7
  * solve whose last unknown, the scale, is solved only where its pivot says it is observable, and a pose and scale update,
  * all on the device, as hand-written HIP kernels for gfx950 (MI355X).  The library takes the maps and never sees the volume.
- * It restates the rigid tracker of include/scsfm_track.h in full and shares no code with it: with a scale of 1 that is
- * never solved (min_scale_pivot = +inf) every pose it gives has the bits of libscsfm_track.so's.
+ * It states the rigid tracker of include/scsfm_track.h again in full, with the scale, and the two libraries are built from
+ * one core (sc-sfmlearner-release_amd/csrc_icp/scsfm_icp.h): with a scale of 1 that is never solved (min_scale_pivot = +inf)
+ * every pose it gives has the bits of libscsfm_track.so's.
  *
  * Conventions (as include/scsfm_cast.h)
  *  - All pointers are DEVICE pointers; the caller owns every buffer; nothing is retained.

@@ -53,9 +53,15 @@ def lib_sources(name):
     return sorted(glob.glob(os.path.join(find(name).csrc, "*.hip")))
 
 
+# What a row's sources include from outside its own directory and header, by a relative path (no -I): the two trackers'
+# point-to-plane ICP core.  It belongs to no row; the ids of the rows that include it cover it.
+ICP_CORE = os.path.join(os.path.dirname(HERE), "csrc_icp", "scsfm_icp.h")
+SHARED_DEPS = {"track": [ICP_CORE], "sim3": [ICP_CORE]}
+
+
 def lib_deps(name):
     row = find(name)
-    return lib_sources(name) + sorted(glob.glob(os.path.join(row.csrc, "*.h"))) + [row.header]
+    return lib_sources(name) + sorted(glob.glob(os.path.join(row.csrc, "*.h"))) + [row.header] + SHARED_DEPS.get(name, [])
 
 
 def _hash(files, extra=()):
@@ -71,8 +77,8 @@ def _hash(files, extra=()):
 
 def lib_source_id(name):
     """First 16 hex digits of the sha256 over everything the library is built from: its own sources (names and contents,
-    sorted), its header and the compiler flags / target architecture.  It is compiled into the binary
-    (<prefix>source_id) so that a loaded .so can be tied to the sources next to it."""
+    sorted), its header, what SHARED_DEPS names for it and the compiler flags / target architecture.  It is compiled into
+    the binary (<prefix>source_id) so that a loaded .so can be tied to the sources next to it."""
     return _hash(lib_deps(name))
 
 

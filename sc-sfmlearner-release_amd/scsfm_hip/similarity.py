@@ -3,8 +3,8 @@ a seventh degree of freedom, the scale of the frame's own depth.  The nets' dept
 sequence, and a rigid tracker trades a frame's scale error for a wrong pose; here every frame carries a scale sigma, its
 depth enters as sigma times the prediction, and the 7 x 7 system of an iteration is solved with the scale last, so that its
 pivot alone decides whether the scale is solved or held at its value -- a frame that sees nothing but planes takes the
-rigid step, bit for bit.  37 sums per frame are reduced in a fixed order; an iteration is two launches for all V frames
-and nothing is copied to the host.
+rigid step, bit for bit (the two libraries compile one core, csrc_icp/scsfm_icp.h).  37 sums per frame are reduced in a
+fixed order; an iteration is two launches for all V frames and nothing is copied to the host.
 
     vol = fusion.Volume(dims, origin, 0.05, device="cuda")
     vol.integrate(disp[:1], images[:1], c2w[:1], K)
@@ -31,7 +31,7 @@ import torch
 
 from . import _lib, raycast
 from .raycast import _check, _ptr, _stream
-from .tracking import _frames
+from .tracking import _check_maps, _frames, _posed_frames
 
 MAX_ITERATIONS = 64
 # The smallest ratio of the scale's LDL^T pivot to the largest diagonal entry of the 7 x 7 matrix at which the scale is
@@ -98,19 +98,10 @@ def align(depth_or_disp, guess, scale0, K, ref_view, model_depth, model_normal, 
     (float32 [V, 16], raycast.views) -> Track.  A pair is dropped when frame and model point are further apart than
     ``max_dist``.  The scale of a frame is solved in an iteration whose scale pivot ratio is above ``min_scale_pivot``
     (``math.inf``: never) and held otherwise."""
-    d = _frames(depth_or_disp)
-    V, H, W = d.shape
-    _check("guess", guess, torch.float64)
-    if guess.numel() != 12 * V or guess.shape[-1] not in (4, 12):
-        raise ValueError(f"guess must be [{V}, 3, 4], got {list(guess.shape)}")
-    dev = d.device
+    d = _posed_frames(depth_or_disp, guess)
+    (V, H, W), dev = d.shape, d.device
     _scales("scale0", scale0, V, dev)
-    _check("K", K, torch.float32, (3, 3))
-    _check("ref_view", ref_view, torch.float32, (V, 16))
-    _check("model_depth", model_depth, torch.float32, (V, H, W))
-    _check("model_normal", model_normal, torch.float32, (V, 3, H, W))
-    if any(t.device != dev for t in (guess, K, ref_view, model_depth, model_normal)):
-        raise ValueError("the frames, the poses and the model maps must live on the same device")
+    _check_maps(d, guess, K, ref_view, model_depth, model_normal)
     iterations, min_pairs, min_scale_pivot = int(iterations), int(min_pairs), float(min_scale_pivot)
     if not 1 <= iterations <= MAX_ITERATIONS:
         raise ValueError(f"iterations must be 1 .. {MAX_ITERATIONS}, got {iterations}")

@@ -50,24 +50,35 @@ def _frames(depth_or_disp):
     return d
 
 
+def _posed_frames(depth_or_disp, guess):
+    """The frames of ``align``, here and in scsfm_hip.similarity, as [V, H, W], with their poses checked."""
+    d = _frames(depth_or_disp)
+    _check("guess", guess, torch.float64)
+    if guess.numel() != 12 * len(d) or guess.shape[-1] not in (4, 12):
+        raise ValueError(f"guess must be [{len(d)}, 3, 4], got {list(guess.shape)}")
+    return d
+
+
+def _check_maps(d, guess, K, ref_view, model_depth, model_normal):
+    """What ``align`` asks of the intrinsics and the model maps of the frames ``d``, and that all share a device."""
+    V, H, W = d.shape
+    _check("K", K, torch.float32, (3, 3))
+    _check("ref_view", ref_view, torch.float32, (V, 16))
+    _check("model_depth", model_depth, torch.float32, (V, H, W))
+    _check("model_normal", model_normal, torch.float32, (V, 3, H, W))
+    if any(t.device != d.device for t in (guess, K, ref_view, model_depth, model_normal)):
+        raise ValueError("the frames, the poses and the model maps must live on the same device")
+
+
 def align(depth_or_disp, guess, K, ref_view, model_depth, model_normal, *, is_disp=True, near=0.0, max_depth=10.0,
           iterations=10, max_dist, min_pairs=64):
     """Aligns V frames -- the nets' disparity (``is_disp``) or a depth, float32 [V, 1, H, W] or [V, H, W] -- from the
     poses ``guess`` (float64 [V, 3, 4], camera to world) to the model maps ``model_depth`` [V, H, W] and ``model_normal``
     [V, 3, H, W] that raycast.cast wrote for the view records ``ref_view`` (float32 [V, 16], raycast.views) -> Track.
     A pair is dropped when frame and model point are further apart than ``max_dist``."""
-    d = _frames(depth_or_disp)
-    V, H, W = d.shape
-    _check("guess", guess, torch.float64)
-    if guess.numel() != 12 * V or guess.shape[-1] not in (4, 12):
-        raise ValueError(f"guess must be [{V}, 3, 4], got {list(guess.shape)}")
-    _check("K", K, torch.float32, (3, 3))
-    _check("ref_view", ref_view, torch.float32, (V, 16))
-    _check("model_depth", model_depth, torch.float32, (V, H, W))
-    _check("model_normal", model_normal, torch.float32, (V, 3, H, W))
-    dev = d.device
-    if any(t.device != dev for t in (guess, K, ref_view, model_depth, model_normal)):
-        raise ValueError("the frames, the poses and the model maps must live on the same device")
+    d = _posed_frames(depth_or_disp, guess)
+    _check_maps(d, guess, K, ref_view, model_depth, model_normal)
+    (V, H, W), dev = d.shape, d.device
     iterations, min_pairs = int(iterations), int(min_pairs)
     if not 1 <= iterations <= MAX_ITERATIONS:
         raise ValueError(f"iterations must be 1 .. {MAX_ITERATIONS}, got {iterations}")

@@ -13,7 +13,7 @@ import subprocess
 
 import numpy as np
 
-from scsfm_hip import libraries
+from scsfm_hip import build as build_py, libraries
 from scsfm_hip._lib import TRACK_ABI_VERSION, TRACK_HEADER, CLib
 
 from _hostsim_fuse import _Call as _FuseCall, _ptr
@@ -32,7 +32,7 @@ def sources():
 def build(force=False):
     row = libraries.find("track")
     srcs = sources()
-    deps = srcs + [os.path.join(HOSTSIM, "hip", "hip_runtime.h"), row.header, os.path.abspath(__file__)]
+    deps = srcs + [os.path.join(HOSTSIM, "hip", "hip_runtime.h"), row.header, build_py.ICP_CORE, os.path.abspath(__file__)]
     if not force and os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
         return LIB
     os.makedirs(os.path.dirname(LIB), exist_ok=True)

@@ -1,8 +1,9 @@
 """libscsfm_sim3.so, the twenty-sixth library (scsfm_hip.libraries.ADDED): the row stands in the open-ended tuple and
 REGISTRY covers it; the header declares exactly the entry points; the library builds with hipcc for gfx950 (no GPU needed),
 exports exactly them and carries the tree's source id; no other library's source id sees csrc_sim3, and csrc_sim3 includes
-nothing of another library; bad arguments are rejected with -1 (sizes with 0) before any pointer is touched; no kernel uses
-scratch or spills a register; build() reports the library among ADDED's lines, ahead of cast's, in cast's wording."""
+nothing of another library (the ICP core it shares with csrc_track belongs to neither); bad arguments are rejected with
+-1 (sizes with 0) before any pointer is touched; no kernel uses scratch or spills a register; build() reports the library
+among ADDED's lines, ahead of cast's, in cast's wording."""
 import ctypes
 import os
 import re
@@ -48,12 +49,22 @@ def test_source_ids_are_per_library():
         deps = build.lib_deps(row.name)
         assert deps and not any("csrc_sim3" in p or "scsfm_sim3" in p for p in deps), row.name
         ids.append(build.lib_source_id(row.name))
-    assert all(os.sep + "csrc_sim3" + os.sep in p or p.endswith("scsfm_sim3.h") for p in build.sim3_deps())
+    assert all(os.sep + "csrc_sim3" + os.sep in p or p.endswith("scsfm_sim3.h") or p == build.ICP_CORE
+               for p in build.sim3_deps())
+    assert build.ICP_CORE in build.sim3_deps()
     assert len(set(ids)) == len(ids) and build.sim3_source_id() not in ids
-    # the rigid tracker is restated, not shared: the source includes its own header and no other of the project's
+    # the source includes its own header and the ICP core it shares with csrc_track, and no other of the project's
     (src,) = build.sim3_sources()
-    assert re.findall(r'#include\s+"([^"]+)"', open(src).read()) == ["scsfm_sim3.h"]
+    assert re.findall(r'#include\s+"([^"]+)"', open(src).read()) == ["scsfm_sim3.h", "../csrc_icp/scsfm_icp.h"]
     assert not re.findall(r'#include\s+"', open(_lib.SIM3_HEADER).read())
+    # the core belongs to no row: exactly the two trackers' ids cover it, and it includes nothing of the project's
+    assert os.path.samefile(build.ICP_CORE, os.path.join(os.path.dirname(src), "../csrc_icp/scsfm_icp.h"))
+    for row in libraries.REGISTRY:
+        assert (build.ICP_CORE in build.lib_deps(row.name)) == (row.name in ("track", "sim3")), row.name
+    core = open(build.ICP_CORE).read()
+    assert not re.findall(r'#include\s+"', core) and not re.findall(r"#include\s+<[^>]*scsfm", core)
+    every = [build.lib_source_id(row.name) for row in libraries.REGISTRY]
+    assert len(set(every)) == len(every)
 
 
 def test_header_declares_exactly_the_entry_points():
